@@ -21,20 +21,40 @@ decides JCT. Work scales with N (jobs per GPU fixed: weak scaling). The real
 NSDI'19 trace is not shipped with the reference and there is no network, so
 the trace is synthetic (``data`` says so).
 
-Fairness of the comparison (``vs_baseline``): after the timed steps, the same
-trace is replayed once under the reference's default FIFO + YARN-CS on the
-same GPUs with the SAME sharing setting; ``vs_baseline`` = Tiresias avg JCT /
-FIFO avg JCT (< 1 is better), the comparison BASELINE.md defines until the
-real trace exists. The Gittins/expected-remaining prior, when a policy needs
-one, comes from a held-out history trace (different seed), never from the
-replayed jobs.
+A plain run does only what the headline needs: set-up, ``--warmup`` replays,
+``--steps`` timed replays, the optional ``--dump-outputs``, the JSON line.
+``ms_per_step`` is the wall time of one timed replay in milliseconds.
 
-Time budget: the driver runs ``--steps 20 --warmup 5`` under a 600 s limit.
-A guard (``--budget-s``, measured from process start) stops early — before a
-step that would not fit — and the JSON line then reports the steps actually
-timed (``steps`` < ``steps_requested``).
+``--full`` adds the untimed comparison replays after the timed steps.
+Fairness of the comparison (``vs_baseline``): the same trace is replayed once
+under the reference's default FIFO + YARN-CS on the same GPUs with the SAME
+sharing setting; ``vs_baseline`` = Tiresias avg JCT / FIFO avg JCT (< 1 is
+better), the comparison BASELINE.md defines until the real trace exists. At
+N > 1 one more replay uses the unscaled 2D-LAS queue limits, and one replay
+runs without the warm trainer pool (cold-build JCT). Without ``--full`` these
+fields of the JSON line are null. The Gittins/expected-remaining prior, when a
+policy needs one, comes from a held-out history trace (different seed), never
+from the replayed jobs.
 
-  python bench.py --gpus N --steps K --warmup W
+``--dump-outputs DIR`` writes what the last timed replay computed as
+``DIR/<name>.npy`` (float64): ``final_loss`` -- the training loss every job
+reported after its last iteration, in trace order -- and ``job_iterations``,
+the iterations each job trained. Every job's weights and batch are seeded by
+its trace index, so these do not depend on how the scheduler interleaved the
+jobs: two builds run with the same arguments can be compared job for job.
+(Measured on MI355X, two runs of one build: the 3-5 iteration jobs, most of
+the trace, agree bit for bit; longer conv / attention jobs drift by up to a
+few 1e-2 relative, as their kernels' atomic accumulation order is not fixed
+and training amplifies the rounding.)
+
+Time budget: ``--steps`` and ``--warmup`` are run as given. ``--budget-s`` (or
+``TAM_BENCH_BUDGET_S``), measured from process start, makes a guard stop early
+— before a step that would not fit — and the JSON line then reports the
+steps actually timed (``steps`` < ``steps_requested``). The ``--full`` replays
+are always guarded (270 s unless a budget is given): one that would not fit is
+skipped.
+
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -243,8 +263,15 @@ def main():
                     help="scheduling round, seconds (0.01: N=1 avg JCT 0.1576 vs 0.1606 s at 0.02 on one "
                          "box, profiles/r5/quantum_ab.md; N>1 rounds end early anyway in fill mode)")
     ap.add_argument("--seed", type=int, default=2019)
-    ap.add_argument("--budget-s", type=float, default=float(os.environ.get("TAM_BENCH_BUDGET_S", 270)),
-                    help="wall budget from process start; steps that would not fit are skipped")
+    ap.add_argument("--budget-s", type=float,
+                    default=float(os.environ["TAM_BENCH_BUDGET_S"]) if "TAM_BENCH_BUDGET_S" in os.environ else None,
+                    help="wall budget from process start; steps that would not fit are skipped "
+                         "(default: none for the warm-up and timed steps, 270 s for the --full replays)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also replay the baseline policy (vs_baseline), the unscaled "
+                         "queue limits (N > 1) and the no-pool configuration, one untimed replay each")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed replay's per-job results as DIR/<name>.npy")
     ap.add_argument("--cpu", action="store_true", help="gloo/CPU rehearsal with tiny models")
     ap.add_argument("--no-graph", action="store_true",
                     help="disable hipGraph capture of 1-GPU jobs' fwd+bwd (eager launches)")
@@ -405,6 +432,7 @@ def main():
         gc.collect()
         gc.disable()
         gc_ms[0] = 0.0
+        last_loss.clear()
         ev0 = (worker.pool_evictions, worker.pressure_spills, worker.pool_hits)
         t = time.perf_counter()
         try:
@@ -428,9 +456,26 @@ def main():
                   file=sys.stderr, flush=True)
         return r, dt
 
-    def fits(longest: float) -> bool:
+    # --dump-outputs: the loss every job reports at the end of a round, as the
+    # controller receives it (the last one is the job's final loss)
+    last_loss = {}
+    if a.dump_outputs:
+        worker_run = worker.run
+
+        def run_recording(plan):
+            rep = worker_run(plan)
+            for jr in rep.get("jobs") or []:
+                if jr.get("loss") is not None and jr.get("iters"):
+                    last_loss[jr["job"]] = jr["loss"]
+            return rep
+
+        worker.run = run_recording
+
+    def fits(longest: float, budget=a.budget_s) -> bool:
         """Every rank takes the same decision (rank 0's clock, broadcast)."""
-        ok = torch.tensor([1 if time.perf_counter() - T_PROC0 + 1.25 * longest <= a.budget_s else 0])
+        if budget is None:
+            return True
+        ok = torch.tensor([1 if time.perf_counter() - T_PROC0 + 1.25 * longest <= budget else 0])
         if world > 1:
             dist.broadcast(ok, 0, group=ctrl_pg)
         return bool(ok.item())
@@ -467,8 +512,30 @@ def main():
         elapsed = float(t.item())
     steps = len(sums)
 
+    # what the last timed replay computed, before any other replay runs
+    final_loss = dict(last_loss)
+    if a.dump_outputs:
+        worker.run = worker_run
+        if world > 1:
+            # a gang's members report the same loss; the lowest rank's is kept
+            got = [None] * world
+            dist.all_gather_object(got, final_loss, group=ctrl_pg)
+            final_loss = {}
+            for d in reversed(got):
+                final_loss.update(d)
+        if rank == 0:
+            import numpy as np
+
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            np.save(os.path.join(a.dump_outputs, "final_loss.npy"),
+                    np.array([final_loss.get(rj.spec.job_id, float("nan")) for rj in jobs], dtype=np.float64))
+            np.save(os.path.join(a.dump_outputs, "job_iterations.npy"),
+                    np.array([rj.iterations for rj in jobs], dtype=np.float64))
+
+    # the comparison replays (--full): each is skipped when it would not fit
+    xbudget = a.budget_s if a.budget_s is not None else 270.0
     base = None
-    if not a.no_baseline and fits(3.0 * longest):
+    if a.full and not a.no_baseline and fits(3.0 * longest, xbudget):
         # FIFO is non-preemptive: its replay can run longer than Tiresias'
         bcfg = make(a.baseline_policy, a.baseline_placement)
         base, _ = replay(bcfg)
@@ -477,10 +544,10 @@ def main():
     # reports that reference-faithful number next to the headline (at N = 1
     # the two configurations are the same)
     unscaled = None
-    if a.scale_limits and n > 1 and fits(1.5 * longest):
+    if a.full and a.scale_limits and n > 1 and fits(1.5 * longest, xbudget):
         unscaled, _ = replay(make(a.policy, a.placement, limits=list(qlim)))
     nopool = None
-    if not a.no_pool and not a.no_nopool_replay and fits(1.5 * longest):
+    if a.full and not a.no_pool and not a.no_nopool_replay and fits(1.5 * longest, xbudget):
         # one replay WITHOUT the warm trainer pool: every job builds its own
         # trainer (allocation, init, eager warm-up, graph capture) inside its
         # JCT -- what a cluster pays when job shapes do not repeat
@@ -539,6 +606,7 @@ def main():
                 "quantum_s": a.quantum,
                 "virtual_nodes": vn or None,
             },
+            "full": a.full,
             "steps_requested": a.steps,
             "warmup_requested": a.warmup,
             "makespan_s": round(makespan, 4),

@@ -200,7 +200,11 @@ def _spill_replay_worker(rank, world, port, outdir):
     from tiresias_amd.executor.cluster_runtime import Worker, run_replay
 
     jobs = bench.bench_trace(world, 4, seed=9, work_s=1.2, tiny=True)
-    cfg = bench.make_cfg("dlas-gpu", "count", world, 9)
+    # attained service is measured wall time, so the queue limits sit far below
+    # what the long jobs run for (0.3-1 s each) on any host: with the default
+    # 1.0 GPU-s limit the longest job ended within a few percent of it, and
+    # whether anything was demoted (and preempted) depended on the CPU's speed
+    cfg = bench.make_cfg("dlas-gpu", "count", world, 9, qlimits=[0.05, 0.3])
     cfg.ckpt_policy = "host"
     w = Worker(rank, world, torch.device("cpu"), dist.group.WORLD)
     s = run_replay(cfg, jobs, rank, world, torch.device("cpu"), ctrl_pg=ctrl,
@@ -291,7 +295,17 @@ def _recover_worker(rank, world, port, outdir, fault, hb_timeout=5.0, gang_timeo
     jobs = bench.bench_trace(world, 4, seed=3, work_s=0.8, min_iters=4, tiny=True)
     for i in (0, 2, 5):                    # gangs spanning the victim rank
         jobs[i].spec.num_gpu = 2 if i != 5 else world - 1
-    if snapshot_s > 0:                     # every job a single replica: a loss needs the snapshot
+    if fault.get("kind", "crash") in ("crash", "hang"):
+        # once a rank is lost, every unfinished gang as wide as the cluster
+        # fails. The trace draws three such gangs, and how many are unfinished
+        # at the fault's round depends on the host's speed (the first round
+        # ends within milliseconds of the last arrival: one round more or less
+        # before the fault). Keep the first one only (it runs, and opens the
+        # whole-cluster communicator, rounds before the fault), so that at most
+        # one job can fail whatever the timing
+        for j in [j for j in jobs if j.spec.num_gpu == world][1:]:
+            j.spec.num_gpu = world - 1
+    if snapshot_s > 0:                    # every job a single replica: a loss needs the snapshot
         for j in jobs:
             j.spec.num_gpu = 1
     cfg = bench.make_cfg("dlas-gpu", "count", world, 3, qlimits=[0.05, 0.3])

@@ -298,7 +298,7 @@ def test_torchrun_bench_world8_cpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--cpu", "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--jobs-per-gpu", "6", "--work-s", "0.08", "--min-iters", "1"]
+           "--jobs-per-gpu", "6", "--work-s", "0.08", "--min-iters", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path), env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]

@@ -189,8 +189,9 @@ def test_bench_trace_is_scheduler_bound():
 
 
 def test_bench_cpu_driver_contract(tmp_path):
-    """``bench.py --cpu --steps 20 --warmup 5`` (the driver's arguments) must
-    finish well inside its budget and print one valid JSON line."""
+    """``bench.py --cpu --steps 20 --warmup 5 --full`` (the driver's arguments,
+    with the baseline replay) must finish well inside its budget and print one
+    valid JSON line."""
     import json as _json
     import subprocess
     import sys
@@ -202,7 +203,8 @@ def test_bench_cpu_driver_contract(tmp_path):
     # thread pool (not the bench) dominates the wall time
     env = dict(os.environ, OMP_NUM_THREADS="2")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--cpu", "--steps", "20",
-                        "--warmup", "5", "--jobs-per-gpu", "48", "--work-s", "0.05", "--min-iters", "1"],
+                        "--warmup", "5", "--jobs-per-gpu", "48", "--work-s", "0.05", "--min-iters", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=240, cwd=str(tmp_path), env=env)
     wall = _t.perf_counter() - t
     assert r.returncode == 0, r.stderr[-3000:]
@@ -213,6 +215,45 @@ def test_bench_cpu_driver_contract(tmp_path):
     assert (d["steps"], d["warmup"]) == (20, 5), (d["steps"], d["warmup"], d.get("process_wall_s"))
     assert d["finished_jobs"] == 48 and d["value"] > 0 and d["vs_baseline"] is not None
     assert d["ms_per_step"] * d["steps"] / 1e3 < wall
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run times exactly ``--steps`` replays and runs no comparison
+    replay (those are behind ``--full``); ``--dump-outputs`` writes the last
+    timed replay's per-job results, identical from run to run."""
+    import json as _json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    env.pop("TAM_BENCH_BUDGET_S", None)
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"d{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--cpu", "--steps", "2", "--warmup", "1",
+                            "--jobs-per-gpu", "12", "--work-s", "0.02", "--min-iters", "2",
+                            "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=120, cwd=str(tmp_path), env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+        assert len(lines) == 1
+        line = _json.loads(lines[0])
+        assert (line["steps"], line["warmup"], line["replays"]) == (2, 1, 3)
+        assert line["ms_per_step"] > 0 and not line["full"]
+        assert line["vs_baseline"] is None and line["no_pool_replay_avg_jct_s"] is None
+        assert sorted(p.name for p in d.iterdir()) == ["final_loss.npy", "job_iterations.npy"]
+        outs.append((np.load(d / "final_loss.npy"), np.load(d / "job_iterations.npy")))
+    jobs = bench.bench_trace(1, 12, 2019, work_s=0.02, min_iters=2, tiny=True)
+    for loss, iters in outs:
+        assert loss.dtype == np.float64 and iters.dtype == np.float64
+        assert loss.shape == (12,) and np.isfinite(loss).all()
+        assert iters.tolist() == [float(j.iterations) for j in jobs]
+    assert np.array_equal(outs[0][0], outs[1][0])
 
 
 def bench_metric():

@@ -15,12 +15,12 @@ run() {  # run <name> <timeout> <cmd...>
   echo "=== [$name] rc=$rc"; tail -n 3 "gpurun_out/$name.err"
   [ $rc -eq 0 ] || exit $rc
 }
-N2="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --no-nopool-replay"
+N2="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --full --no-nopool-replay"
 for mode in "$@"; do
   case $mode in
     n2fill) run n2_fill 400 env TAM_SHARED_GPU=1 TAM_FILL=1 $N2 ;;
     n2nofill) run n2_nofill 400 env TAM_SHARED_GPU=1 TAM_FILL=0 $N2 ;;
-    n1q20) run n1_q20 300 python bench.py --steps 5 --warmup 2 --quantum 0.02 --no-nopool-replay ;;
-    n1q10) run n1_q10 300 python bench.py --steps 5 --warmup 2 --quantum 0.01 --no-nopool-replay ;;
+    n1q20) run n1_q20 300 python bench.py --steps 5 --warmup 2 --quantum 0.02 --full --no-nopool-replay ;;
+    n1q10) run n1_q10 300 python bench.py --steps 5 --warmup 2 --quantum 0.01 --full --no-nopool-replay ;;
   esac
 done
