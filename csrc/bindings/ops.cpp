@@ -1113,9 +1113,19 @@ static const unsigned* guard_ptr(const optional<Tensor>& guard, const Tensor& li
               "tam: guard must be an int32 [2] tensor on the parameters' device");
   return (const unsigned*)guard->data_ptr<int>();
 }
+// clip (optional float32 [4], 16-B aligned): the record grad_clip_finalize
+// writes; clip[0] scales the gradient, a negative clip[0] skips the step
+static const float* clip_ptr(const optional<Tensor>& clip, const Tensor& like) {
+  if (!(clip.has_value() && clip->defined())) return nullptr;
+  TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->numel() >= 4 && clip->is_contiguous() &&
+                  clip->device() == like.device() && (((uintptr_t)clip->data_ptr()) & 15) == 0,
+              "tam: clip must be a 16-B aligned float32 [4] tensor on the parameters' device");
+  return clip->data_ptr<float>();
+}
 void sgd_op(const Tensor& w, const Tensor& g, const Tensor& mom, const Tensor& wb, double lr,
             double momentum, double wd, double gscale, bool nesterov, bool zero_grad,
-            const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until) {
+            const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until,
+            const optional<Tensor>& clip) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(mom, "mom"); check_bf16(wb, "wb");
   TORCH_CHECK(w.numel() % 4 == 0 && g.numel() == w.numel() && mom.numel() == w.numel() &&
                   wb.numel() == w.numel(),
@@ -1123,19 +1133,43 @@ void sgd_op(const Tensor& w, const Tensor& g, const Tensor& mom, const Tensor& w
   TORCH_CHECK(zero_from % 4 == 0 && (wd_until < 0 || wd_until % 4 == 0), "tam.sgd: region bounds % 4");
   tam::sgd_step(w.data_ptr<float>(), g.data_ptr<float>(), mom.data_ptr<float>(), bpm(wb), w.numel(),
                 (float)lr, (float)momentum, (float)wd, (float)gscale, nesterov, zero_grad,
-                cur_stream(w), guard_ptr(guard, w), (long)zero_from, (long)wd_until);
+                cur_stream(w), guard_ptr(guard, w), (long)zero_from, (long)wd_until, clip_ptr(clip, w));
 }
 void adam_op(const Tensor& w, const Tensor& g, const Tensor& m, const Tensor& v, const Tensor& wb,
              double lr, double b1, double b2, double eps, double wd, int64_t step, double gscale,
-             bool zero_grad, const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until) {
+             bool zero_grad, const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until,
+             const optional<Tensor>& clip) {
   check_f32(w, "w"); check_f32(g, "g"); check_f32(m, "m"); check_f32(v, "v"); check_bf16(wb, "wb");
   TORCH_CHECK(w.numel() % 4 == 0, "tam.adam: numel % 4");
   TORCH_CHECK(zero_from % 4 == 0 && (wd_until < 0 || wd_until % 4 == 0), "tam.adam: region bounds % 4");
   tam::adam_step(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(),
                  bpm(wb), w.numel(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
                  (int)step, (float)gscale, zero_grad, cur_stream(w), guard_ptr(guard, w), (long)zero_from,
-                 (long)wd_until);
+                 (long)wd_until, clip_ptr(clip, w));
 }
+// global-norm gradient clip (optim.hip): g -> one fp64 partial per block ->
+// the clip record the optimizer steps take
+void grad_sumsq_op(const Tensor& g, const Tensor& partials) {
+  check_f32(g, "g"); check_contig(g, "g"); check_dev(partials, "partials"); check_contig(partials, "partials");
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials.device() == g.device(),
+              "tam.grad_sumsq: partials must be float64 on the gradient's device");
+  TORCH_CHECK(g.numel() % 4 == 0 && (((uintptr_t)g.data_ptr()) & 15) == 0,
+              "tam.grad_sumsq: numel % 4 and a 16-B aligned gradient");
+  const int blocks = tam::grad_sumsq_blocks(g.numel());
+  TORCH_CHECK(partials.numel() >= blocks && partials.numel() <= (1 << 20), "tam.grad_sumsq: partials holds ",
+              partials.numel(), " slots, the grid needs ", blocks);
+  tam::grad_sumsq(g.data_ptr<float>(), g.numel(), partials.data_ptr<double>(), (int)partials.numel(),
+                  cur_stream(g));
+}
+void grad_clip_finalize_op(const Tensor& partials, double max_norm, double gscale, const Tensor& clip) {
+  check_dev(partials, "partials"); check_contig(partials, "partials"); check_f32(clip, "clip");
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials.numel() >= 1 && partials.numel() <= (1 << 20),
+              "tam.grad_clip_finalize: partials must be a float64 tensor of the grad_sumsq slots");
+  TORCH_CHECK(max_norm > 0.0, "tam.grad_clip_finalize: max_norm must be > 0");
+  tam::grad_clip_finalize(partials.data_ptr<double>(), (int)partials.numel(), (float)max_norm, (float)gscale,
+                          const_cast<float*>(clip_ptr(clip, partials)), cur_stream(partials));
+}
+int64_t grad_sumsq_blocks_op(int64_t n) { return tam::grad_sumsq_blocks((long)n); }
 void lstm_guard_step_op(const Tensor& err) {
   TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 2,
               "tam.lstm_guard_step: err must be an int32 [2] GPU tensor");
@@ -1369,8 +1403,11 @@ TORCH_LIBRARY(tam, m) {
   m.def("relu_backward(Tensor dy, Tensor y, Tensor(a!) dx) -> ()", &relu_backward_op);
   m.def("add(Tensor a, Tensor b, Tensor(a!) y) -> ()", &add_op);
   m.def("cast_f32_bf16(Tensor x, Tensor(a!) y) -> ()", &cast_op);
-  m.def("sgd_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1) -> ()", &sgd_op);
-  m.def("adam_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1) -> ()", &adam_op);
+  m.def("sgd_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &sgd_op);
+  m.def("adam_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adam_op);
+  m.def("grad_sumsq(Tensor g, Tensor(a!) partials) -> ()", &grad_sumsq_op);
+  m.def("grad_clip_finalize(Tensor partials, float max_norm, float gscale, Tensor(a!) clip) -> ()", &grad_clip_finalize_op);
+  m.def("grad_sumsq_blocks(int n) -> int", &grad_sumsq_blocks_op);
   m.def("lstm_guard_step(Tensor(a!) err) -> ()", &lstm_guard_step_op);
   m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len) -> ()", &attn_forward_op);
   m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len) -> ()", &attn_backward_op);

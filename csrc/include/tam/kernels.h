@@ -122,11 +122,21 @@ void cast_f32_bf16(const float* x, bf16_t* y, long n, hipStream_t s);
 void optim_grid(int blocks);   // grid cap of the optimizer launches (A/B; 0 = one block per CU)
 void sgd_step(float* w, float* g, float* mom, bf16_t* wb, long n, float lr, float momentum,
               float wd, float gscale, int nesterov, int zero_grad, hipStream_t s,
-              const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1);
+              const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+              const float* clip = nullptr);
 void optim_variant(int v);   // streaming optimizer variants (optim.hip), 0 = baseline
 void adam_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float lr, float b1,
                float b2, float eps, float wd, int step, float gscale, int zero_grad,
-               hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1);
+               hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+               const float* clip = nullptr);
+// global-norm gradient clip: grad_sumsq writes one fp64 partial per block and
+// zeroes partials[blocks..slots); grad_clip_finalize sums them and writes the
+// 16-B clip record {float scale, float norm, u32 non-finite steps, u32
+// clipped steps} that sgd_step / adam_step consume (scale < 0: skip the step)
+int grad_sumsq_blocks(long n);   // blocks grad_sumsq launches over n elements (<= slots)
+void grad_sumsq(const float* g, long n, double* partials, int slots, hipStream_t s);
+void grad_clip_finalize(const double* partials, int slots, float max_norm, float gscale, float* clip,
+                        hipStream_t s);
 
 // fused attention (bf16, head_dim 64): element (b, s, h, d) at b * *_bstride +
 // s * *_stride + 64 h + d (batch-major [B][S][H][64], or a time-major

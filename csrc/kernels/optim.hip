@@ -15,6 +15,12 @@
 // not reach the weights. lstm_guard_step then moves the word into the job's
 // skipped-step count (err[1]), which the worker subtracts from the round's
 // progress and uses to switch the job to the per-step recurrence.
+//
+// ``clip`` (nullable): the 16-B device record grad_clip_finalize writes from
+// the step's global gradient norm (grad_sumsq). clip[0] is the clip scale,
+// folded into gscale once per thread; a negative clip[0] (non-finite norm)
+// takes the guard path. The scale never visits the host.
+#include <cmath>
 #include <cstdlib>
 
 #include "tam/common.h"
@@ -27,12 +33,13 @@ __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ w, float* 
                                                    bf16_t* __restrict__ wb, long n4, float lr,
                                                    float momentum, float wd0, float gscale,
                                                    int nesterov, int zero_grad, const unsigned* guard,
-                                                   long zero_from4, long wd_until4) {
-  if (guard != nullptr && *guard != 0u) {
+                                                   long zero_from4, long wd_until4, const float* clip) {
+  if ((guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f)) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
       if (i >= zero_from4) ((float4*)g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
+  if (clip != nullptr) gscale *= clip[0];
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
        i += (long)gridDim.x * blockDim.x) {
     float4 wv = ((float4*)w)[i];
@@ -60,12 +67,13 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ w, float*
                                                     float b1, float b2, float eps, float wd0,
                                                     float bc1, float bc2, float gscale,
                                                     int zero_grad, const unsigned* guard, long zero_from4,
-                                                    long wd_until4) {
-  if (guard != nullptr && *guard != 0u) {
+                                                    long wd_until4, const float* clip) {
+  if ((guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f)) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
       if (i >= zero_from4) ((float4*)g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
+  if (clip != nullptr) gscale *= clip[0];
   const float ib1 = 1.f / bc1, ib2 = 1.f / bc2;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
        i += (long)gridDim.x * blockDim.x) {
@@ -124,13 +132,14 @@ __global__ void __launch_bounds__(256) adam_stream_kernel(float* __restrict__ w,
                                                            bf16_t* __restrict__ wb, long n4, float lr, float b1,
                                                            float b2, float eps, float wd0, float bc1, float bc2,
                                                            float gscale, int zero_grad, const unsigned* guard,
-                                                           long zero_from4, long wd_until4) {
+                                                           long zero_from4, long wd_until4, const float* clip) {
   const long stride = (long)gridDim.x * blockDim.x;
-  if (guard != nullptr && *guard != 0u) {
+  if ((guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f)) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride)
       if (i >= zero_from4) st4<NT>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
     return;
   }
+  if (clip != nullptr) gscale *= clip[0];
   const float ib1 = 1.f / bc1, ib2 = 1.f / bc2;
   auto body = [&](long i, float4 wv, float4 gv, float4 mv, float4 vv) {
     float* wp = (float*)&wv; float* gp = (float*)&gv; float* mp = (float*)&mv; float* vp = (float*)&vv;
@@ -169,13 +178,14 @@ __global__ void __launch_bounds__(256) sgd_stream_kernel(float* __restrict__ w, 
                                                           float* __restrict__ mom, bf16_t* __restrict__ wb, long n4,
                                                           float lr, float momentum, float wd0, float gscale,
                                                           int nesterov, int zero_grad, const unsigned* guard,
-                                                          long zero_from4, long wd_until4) {
+                                                          long zero_from4, long wd_until4, const float* clip) {
   const long stride = (long)gridDim.x * blockDim.x;
-  if (guard != nullptr && *guard != 0u) {
+  if ((guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f)) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride)
       if (i >= zero_from4) st4<NT>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
     return;
   }
+  if (clip != nullptr) gscale *= clip[0];
   auto body = [&](long i, float4 wv, float4 gv, float4 mv) {
     float* wp = (float*)&wv; float* gp = (float*)&gv; float* mp = (float*)&mv;
     const float wd = i < wd_until4 ? wd0 : 0.f;
@@ -260,36 +270,120 @@ static int ogrid(long n4) {
 // store / decay / no-decay regions (was three launches through round 5)
 void sgd_step(float* w, float* g, float* mom, bf16_t* wb, long n, float lr, float momentum,
               float wd, float gscale, int nesterov, int zero_grad, hipStream_t s, const unsigned* guard,
-              long zero_from, long wd_until) {
+              long zero_from, long wd_until, const float* clip) {
   // n % 4 == 0 (arena segments are padded to 64 elements)
   const dim3 grid(ogrid(n / 4));
   const long zf4 = zero_from / 4, wu4 = wd_until < 0 ? n / 4 : wd_until / 4;
   switch (optim_pick(n / 4, false)) {
     case 3:
       hipLaunchKernelGGL((sgd_stream_kernel<4, true>), grid, dim3(256), 0, s, w, g, mom, wb, n / 4, lr, momentum, wd,
-                         gscale, nesterov, zero_grad, guard, zf4, wu4);
+                         gscale, nesterov, zero_grad, guard, zf4, wu4, clip);
       break;
     default:
       hipLaunchKernelGGL(sgd_kernel, grid, dim3(256), 0, s, w, g, mom, wb, n / 4, lr, momentum, wd, gscale, nesterov,
-                         zero_grad, guard, zf4, wu4);
+                         zero_grad, guard, zf4, wu4, clip);
   }
 }
 
 void adam_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float lr, float b1,
                float b2, float eps, float wd, int step, float gscale, int zero_grad,
-               hipStream_t s, const unsigned* guard, long zero_from, long wd_until) {
+               hipStream_t s, const unsigned* guard, long zero_from, long wd_until, const float* clip) {
   const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
   const dim3 grid(ogrid(n / 4));
   const long zf4 = zero_from / 4, wu4 = wd_until < 0 ? n / 4 : wd_until / 4;
   switch (optim_pick(n / 4, true)) {
     case 3:
       hipLaunchKernelGGL((adam_stream_kernel<4, true>), grid, dim3(256), 0, s, w, g, m, v, wb, n / 4, lr, b1, b2, eps,
-                         wd, bc1, bc2, gscale, zero_grad, guard, zf4, wu4);
+                         wd, bc1, bc2, gscale, zero_grad, guard, zf4, wu4, clip);
       break;
     default:
       hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, s, w, g, m, v, wb, n / 4, lr, b1, b2, eps, wd, bc1, bc2,
-                         gscale, zero_grad, guard, zf4, wu4);
+                         gscale, zero_grad, guard, zf4, wu4, clip);
   }
+}
+
+// ------------------------------------------------- global-norm gradient clip
+// Pass 1, grad_sumsq: one streaming read of the gradient arena on the
+// optimizer's grid (ogrid), U float4 loads in flight per lane. The loads are
+// ordinary, not NT: the optimizer reads the same bytes next, so an arena that
+// fits stays in L2 / MALL. Squares accumulate in fp64 per thread (the pass is
+// memory-bound, vector fp64 FMA is full rate), then wave shuffles + LDS; each
+// block stores ONE fp64 partial into its own slot and the slots past the grid
+// are zeroed, so pass 2 sums a fixed count in a fixed order. No float
+// atomics: for a fixed grid the norm is bitwise reproducible, as the slab
+// split-K and BN reductions are.
+template <int U>
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(const float* __restrict__ g, long n4,
+                                                          double* __restrict__ partials, int slots) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long full = n4 / (U * stride) * (U * stride);
+  double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+  auto acc = [&](float4 v) {
+    a0 = fma((double)v.x, (double)v.x, a0); a1 = fma((double)v.y, (double)v.y, a1);
+    a2 = fma((double)v.z, (double)v.z, a2); a3 = fma((double)v.w, (double)v.w, a3);
+  };
+  for (long base = t; base < full; base += U * stride) {
+    float4 gv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) gv[u] = ((const float4*)g)[base + u * stride];
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc(gv[u]);
+  }
+  for (long i = full + t; i < n4; i += stride) acc(((const float4*)g)[i]);
+  double r = (a0 + a1) + (a2 + a3);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) r += __shfl_down(r, o, 64);
+  __shared__ double wsum[4];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  for (long s = gridDim.x + t; s < slots; s += stride) partials[s] = 0.;
+}
+
+// Pass 2, one block: sumsq = partials[0..P) in a fixed order, then the clip
+// record (4 words, 16 B): [0] float scale, [1] float norm of this step,
+// [2] uint32 non-finite steps, [3] uint32 steps that clipped.
+//   norm = gscale * sqrt(sumsq)
+//   finite:     scale = min(1, max_norm / (norm + 1e-6))   (clip_grad_norm_)
+//   non-finite: scale = -1 -> the optimizer only resets the gradient
+__global__ void __launch_bounds__(256) grad_clip_finalize_kernel(const double* __restrict__ partials, int P,
+                                                                  float max_norm, float gscale, float* clip) {
+  __shared__ double red[256];
+  double a = 0.;
+  for (int i = threadIdx.x; i < P; i += 256) a += partials[i];
+  red[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)((double)gscale * sqrt(red[0]));
+    unsigned* cnt = (unsigned*)clip;
+    float scale = -1.f;
+    if (isfinite(norm)) {
+      // the quotient in fp64: one rounding into the fp32 scale
+      scale = fminf(1.f, (float)((double)max_norm / ((double)norm + 1e-6)));
+      if (scale < 1.f) cnt[3] += 1u;
+    } else {
+      cnt[2] += 1u;
+    }
+    clip[0] = scale;
+    clip[1] = norm;
+  }
+}
+
+int grad_sumsq_blocks(long n) { return ogrid(n / 4); }
+
+void grad_sumsq(const float* g, long n, double* partials, int slots, hipStream_t s) {
+  // n % 4 == 0, slots >= grad_sumsq_blocks(n)
+  hipLaunchKernelGGL((grad_sumsq_kernel<8>), dim3(ogrid(n / 4)), dim3(256), 0, s, g, n / 4, partials, slots);
+}
+
+void grad_clip_finalize(const double* partials, int slots, float max_norm, float gscale, float* clip,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, s, partials, slots, max_norm, gscale, clip);
 }
 
 __global__ void lstm_guard_step_kernel(unsigned* err) {

@@ -6,7 +6,7 @@ polls ``DIR`` every scheduling round (see ``executor/spool.py``).
 Examples::
 
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --gpus 2 --iterations 800
-    python -m tiresias_amd.cli.submit --spool /tmp/tam --model gnmt --duration 30
+    python -m tiresias_amd.cli.submit --spool /tmp/tam --model gnmt --duration 30 --grad-clip 5.0
     python -m tiresias_amd.cli.submit --spool /tmp/tam --status
     python -m tiresias_amd.cli.submit --spool /tmp/tam --shutdown
 """
@@ -28,6 +28,8 @@ def main(argv=None) -> int:
     ap.add_argument("--duration", type=float, help="seconds of service (converted to iterations)")
     ap.add_argument("--job-id")
     ap.add_argument("--batch", type=int)
+    ap.add_argument("--grad-clip", type=float,
+                    help="clip the gradient's global L2 norm to this value; non-finite steps are skipped")
     ap.add_argument("--status", action="store_true")
     ap.add_argument("--shutdown", action="store_true", help="stop serving once the cluster drains")
     a = ap.parse_args(argv)
@@ -42,7 +44,7 @@ def main(argv=None) -> int:
     if not a.model or (a.iterations is None and a.duration is None):
         ap.error("--model and one of --iterations / --duration are required")
     jid = sp.submit(a.model, a.gpus, iterations=a.iterations, duration=a.duration, job_id=a.job_id,
-                    batch=a.batch)
+                    batch=a.batch, grad_clip=a.grad_clip)
     print(jid)
     return 0
 

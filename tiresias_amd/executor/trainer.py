@@ -27,9 +27,14 @@ class Trainer:
                  data_seed: Optional[int] = None, use_graph: bool = False, bucket_mb: float = 32.0,
                  model_kwargs: Optional[dict] = None, lr: Optional[float] = None,
                  overlap_wgrad: Optional[bool] = None, branches: Optional[bool] = None,
-                 ddp_shard: bool = False, ddp_wire: str = "fp32"):
+                 ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None):
         self.model_name = model
         self.spec = MODELS[model]
+        if grad_clip is None:
+            grad_clip = self.spec.clip
+        if grad_clip is not None and ddp_shard and group is not None and comm_size(group) > 1:
+            raise ValueError("grad_clip with ddp_shard is not supported: a sharded gang's global norm needs "
+                             "the replicated tails counted once")
         self.device = torch.device(device)
         if self.device.type == "cuda":
             _lib.load(required=True)
@@ -77,6 +82,13 @@ class Trainer:
         self.branches = getattr(self.model, "branch_default", False) if branches is None else branches
         self._bs: List = []
         self.last_loss: Optional[torch.Tensor] = None
+        # global-norm gradient clip (set_grad_clip); None = off, nothing
+        # allocated or launched
+        self.grad_clip: Optional[float] = None
+        self._clip = None               # device clip record (optim.hip): scale, norm, 2 counters
+        self._clip_part = None          # grad_sumsq's per-block fp64 partials
+        self._clip_host = [1.0, 0.0, 0, 0]   # the same four words on the CPU path
+        self.set_grad_clip(grad_clip)
         # weight init and the synthetic batch were queued on the stream that
         # built the trainer; a step issued from another stream (GPU sharing
         # runs each job on its own stream) must wait for them first
@@ -137,6 +149,57 @@ class Trainer:
                 torch.cuda.current_stream(self.device).wait_stream(s)
         return loss
 
+    # ------------------------------------------------------------ gradient clip
+    def set_grad_clip(self, v: Optional[float]) -> None:
+        """Clip the global L2 norm of the (gang-averaged) gradient to ``v``
+        before every optimizer step; ``None`` turns it off. On the GPU the
+        norm (grad_sumsq), the scale (grad_clip_finalize) and its use (the
+        optimizer kernels' ``clip`` record) stay on the device: no host read
+        and no sync per step. A step whose norm is inf / NaN is skipped -- the
+        gradient is reset, master / optimizer state / shadow are not written
+        -- and still advances ``step_count``, as a guarded LSTM step does.
+        A non-sharded gang needs no extra collective: after the all-reduce
+        every member holds the same gradient and computes the same scale."""
+        if v is not None:
+            v = float(v)
+            if not (v > 0.0 and v != float("inf")):
+                raise ValueError(f"grad_clip must be a finite number > 0, got {v}")
+            if self.ddp is not None and self.ddp.shard:
+                raise ValueError("grad_clip with ddp_shard is not supported: a sharded gang's global norm "
+                                 "needs the replicated tails counted once")
+            if self.device.type == "cuda" and self._clip is None:
+                T = _lib.ops()
+                self._clip = torch.zeros(4, dtype=torch.float32, device=self.device)
+                self._clip_part = torch.zeros(int(T.grad_sumsq_blocks(self.arena.numel)), dtype=torch.float64,
+                                              device=self.device)
+        self.grad_clip = v
+
+    def _clip_launch(self, gscale: float):
+        """The step's clip record (None when clipping is off): two launches on
+        the current stream, after the gradient is final."""
+        if self.grad_clip is None:
+            return None
+        T = _lib.ops()
+        T.grad_sumsq(self.arena.grad, self._clip_part)
+        T.grad_clip_finalize(self._clip_part, self.grad_clip, gscale, self._clip)
+        return self._clip
+
+    def clip_stats(self) -> dict:
+        """``{"last_norm", "last_scale", "nonfinite_steps", "clipped_steps"}``
+        of this job since its start (``reset`` zeroes them): the last step's
+        gradient norm and clip scale (-1 for a skipped non-finite step) and
+        the counts of skipped / clipped steps. A host read: call after the
+        round's synchronize."""
+        if self._clip is not None:
+            rec = self._clip.cpu()
+            cnt = rec.view(torch.int32)
+            st = [float(rec[0]), float(rec[1]), int(cnt[2]), int(cnt[3])]
+        else:
+            st = self._clip_host
+        if self.step_count == 0:
+            st = [1.0, 0.0, st[2], st[3]]
+        return {"last_scale": st[0], "last_norm": st[1], "nonfinite_steps": st[2], "clipped_steps": st[3]}
+
     def _opt_step(self):
         A = self.arena
         gscale = self.ddp.grad_scale if self.ddp is not None else 1.0
@@ -169,17 +232,35 @@ class Trainer:
             T = _lib.ops()
             guard = self.model.err if self.uses_persist else None
             zf = A.n_store if Fx.STORE_GRAD else 0
+            clip = self._clip_launch(gscale)
             if self.opt == "sgd":
                 T.sgd_step(A.master, A.grad, self.opt_state[0], A.shadow, self.lr, 0.9, self.spec.wd, gscale, False,
-                           True, guard, zf, A.n_decay)
+                           True, guard, zf, A.n_decay, clip)
             else:
                 T.adam_step(A.master, A.grad, self.opt_state[0], self.opt_state[1], A.shadow, self.lr, 0.9, 0.98,
-                            1e-9, self.spec.wd, self.step_count, gscale, True, guard, zf, A.n_decay)
+                            1e-9, self.spec.wd, self.step_count, gscale, True, guard, zf, A.n_decay, clip)
             if self.uses_persist:
                 _lib.ops().lstm_guard_step(self.model.err)
             return
         else:
             regions = [(0, A.n_decay, self.spec.wd), (A.n_decay, A.numel, 0.0)]
+            if self.grad_clip is not None:
+                # the device path in plain torch: same formula, same skip
+                norm = gscale * float(A.grad.double().norm())
+                st = self._clip_host
+                if norm == norm and abs(norm) != float("inf"):
+                    scale = min(1.0, self.grad_clip / (norm + 1e-6))
+                    st[3] += scale < 1.0
+                    gscale = gscale * scale
+                else:
+                    scale = -1.0
+                    st[2] += 1
+                    A.grad.zero_()
+                    regions = []
+                st[0], st[1] = scale, norm
+        # (the per-region device launches below are the sharded gang's, where
+        # clipping is rejected: clip is None there)
+        clip = None
         A.grad_epoch += 1
         for reg in regions:
             lo, hi, wd = reg[:3]
@@ -193,10 +274,11 @@ class Trainer:
                 # job's own timeout word) only resets the gradient
                 guard = self.model.err if self.uses_persist else None
                 if self.opt == "sgd":
-                    T.sgd_step(w, g, self.opt_state[0][lo:hi], wb, self.lr, 0.9, wd, gscale, False, zero, guard)
+                    T.sgd_step(w, g, self.opt_state[0][lo:hi], wb, self.lr, 0.9, wd, gscale, False, zero, guard,
+                               0, -1, clip)
                 else:
                     T.adam_step(w, g, self.opt_state[0][lo:hi], self.opt_state[1][lo:hi], wb, self.lr,
-                                0.9, 0.98, 1e-9, wd, self.step_count, gscale, zero, guard)
+                                0.9, 0.98, 1e-9, wd, self.step_count, gscale, zero, guard, 0, -1, clip)
             else:
                 _cpu_opt(self.opt, w, g, self.opt_state, lo, hi, wb, self.lr, wd, gscale, self.step_count)
         if sharded:
@@ -489,6 +571,9 @@ class Trainer:
             self.data[k].copy_(v)
         self.step_count = 0
         self.last_loss = None
+        if self._clip is not None:
+            self._clip.zero_()
+        self._clip_host = [1.0, 0.0, 0, 0]
         if self.device.type == "cuda":
             self._ready = torch.cuda.Event()
             self._ready.record(torch.cuda.current_stream(self.device))
@@ -497,6 +582,8 @@ class Trainer:
     def rebind(self, group) -> None:
         """Move the job to a new DDP gang (after a preemption resumed it on
         different GPUs): new communicator, fresh bucketer."""
+        if self.grad_clip is not None and self.ddp_shard and group is not None and comm_size(group) > 1:
+            raise ValueError("grad_clip with ddp_shard is not supported")
         # sharded state survives only a re-created communicator over the SAME
         # rank set (same member positions); anything else needs consolidate()
         dirty = self.state_sharded

@@ -11,7 +11,7 @@ from __future__ import annotations
 import os
 
 from dataclasses import dataclass, field
-from typing import Any, Callable, Dict
+from typing import Any, Callable, Dict, Optional
 
 import torch
 
@@ -42,6 +42,9 @@ class ModelSpec:
     # Linear weight gradients deferred and issued as ONE grouped launch per
     # backward (ops/functional.py defer_wgrad; 1-GPU jobs)
     group_wgrad: bool = False
+    # global-norm gradient clip of the job's recipe (executor/trainer.py);
+    # None = off. No shipped model sets it: a job asks for it (--grad-clip)
+    clip: Optional[float] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

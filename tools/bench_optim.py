@@ -1,6 +1,11 @@
 """Fused optimizer kernels (csrc/kernels/optim.hip) on the model arenas'
 sizes: achieved HBM bandwidth of one SGD-momentum / AdamW step (bytes =
-master+grad+state reads, master+state+grad-zero+bf16 shadow writes)."""
+master+grad+state reads, master+state+grad-zero+bf16 shadow writes).
+
+``--clip`` also times, per arena at the production variant / grid, the
+global-norm pass alone (grad_sumsq + grad_clip_finalize, 4 B/param read) and
+the optimizer step with and without the norm pass + ``clip`` record in front
+of it (the difference is what clipping adds to a step)."""
 import json
 import os
 import sys
@@ -24,6 +29,9 @@ def timeit(fn, iters=20):
 
 
 def main():
+    clip_rows = "--clip" in sys.argv
+    if clip_rows:
+        sys.argv.remove("--clip")
     _lib.load(required=True)
     T = _lib.ops()
     dev = torch.device("cuda", 0)
@@ -50,6 +58,33 @@ def main():
             out.append(r)
         T.optim_variant(-1)
         T.optim_grid(0)
+        if clip_rows:
+            part = torch.zeros(int(T.grad_sumsq_blocks(n)), dtype=torch.float64, device=dev)
+            rec = torch.zeros(4, device=dev)
+
+            def norm():
+                T.grad_sumsq(g, part)
+                T.grad_clip_finalize(part, 5.0, 1.0, rec)
+
+            def step(c):
+                if opt == "sgd":
+                    T.sgd_step(w, g, m, wb, 0.1, 0.9, 1e-4, 1.0, False, True, None, 0, -1, c)
+                else:
+                    T.adam_step(w, g, m, v, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, 3, 1.0, True, None, 0, -1, c)
+
+            def clipped():
+                norm()
+                step(rec)
+
+            for _ in range(2):                                                # two interleaved rounds
+                for kind, fn, nb in (("norm", norm, 4 * n), ("step", lambda: step(None), nbytes),
+                                     ("norm+step_clip", clipped, nbytes + 4 * n)):
+                    us = timeit(fn)
+                    r = dict(model=name, opt=opt, kind=kind, params=n, us=round(us, 1),
+                             tb_per_s=round(nb / us / 1e6, 2))
+                    print(json.dumps(r), flush=True)
+                    out.append(r)
+            del part, rec
         del v
         del w, g, m, wb
         torch.cuda.empty_cache()
