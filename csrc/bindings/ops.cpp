@@ -806,10 +806,30 @@ void bn_backward_op(const Tensor& dy, const optional<Tensor>& y, const Tensor& x
                    sp, sums_ready ? 1 : 0, has_mask ? ymask->data_ptr<uint8_t>() : nullptr, cur_stream(x));
 }
 
+// the dropout arguments of the LN ops / dropout_apply: rec (optional int32
+// [4] {seed, stream, step, 0} on the data's device), site, thr = round(p *
+// 65536) in (0, 65536), scale = 65536 / (65536 - thr); no rec = no dropout
+static tam::LnDrop drop_args(const optional<Tensor>& rec, int64_t site, int64_t thr, double scale,
+                             const Tensor& like, const char* op) {
+  tam::LnDrop d;
+  if (!(rec.has_value() && rec->defined())) return d;
+  TORCH_CHECK(rec->scalar_type() == at::kInt && rec->numel() >= 4 && rec->is_contiguous() &&
+                  rec->device() == like.device(),
+              op, ": drop_rec must be an int32 [4] tensor on the data's device");
+  TORCH_CHECK(thr > 0 && thr < 65536 && site >= 0 && site <= 0x7fffffff, op, ": drop_thr in (0, 65536), drop_site >= 0");
+  d.rec = rec->data_ptr<int>();
+  d.site = (unsigned)site;
+  d.thr = (unsigned)thr;
+  d.scale = (float)scale;
+  return d;
+}
+
 // addend / sum_out (both or neither): y = LN(x + addend), sum_out = x + addend
+// drop_rec (with addend): sum_out = x + dropout(addend)
 void ln_forward_op(const Tensor& x, const Tensor& g, const Tensor& b, const Tensor& y,
                    const Tensor& mean, const Tensor& rstd, double eps, const optional<Tensor>& addend,
-                   const optional<Tensor>& sum_out) {
+                   const optional<Tensor>& sum_out, const optional<Tensor>& drop_rec, int64_t drop_site,
+                   int64_t drop_thr, double drop_scale) {
   check_bf16(x, "x"); check_bf16(y, "y"); check_contig(x, "x"); check_contig(y, "y");
   check_f32(g, "g"); check_f32(b, "b");
   const int64_t D = x.size(-1);
@@ -821,14 +841,27 @@ void ln_forward_op(const Tensor& x, const Tensor& g, const Tensor& b, const Tens
     check_bf16(*sum_out, "sum_out"); check_contig(*sum_out, "sum_out");
     TORCH_CHECK(addend->numel() == x.numel() && sum_out->numel() == x.numel(), "tam.ln_forward: addend size");
   }
+  const tam::LnDrop drop = drop_args(drop_rec, drop_site, drop_thr, drop_scale, x, "tam.ln_forward");
+  TORCH_CHECK(!drop.rec || add, "tam.ln_forward: drop_rec needs addend");
   tam::ln_forward(bp(x), g.data_ptr<float>(), b.data_ptr<float>(), bpm(y), mean.data_ptr<float>(),
                   rstd.data_ptr<float>(), x.numel() / D, (int)D, (float)eps, cur_stream(x),
-                  add ? bp(*addend) : nullptr, add ? bpm(*sum_out) : nullptr);
+                  add ? bp(*addend) : nullptr, add ? bpm(*sum_out) : nullptr, drop);
+}
+
+// dr + drop_rec (both or neither): dr = keep ? dx * scale : 0
+static tam::bf16_t* ln_dres(const optional<Tensor>& dr, const tam::LnDrop& drop, const Tensor& x, const char* op) {
+  const bool has = dr.has_value() && dr->defined();
+  TORCH_CHECK(has == (drop.rec != nullptr), op, ": dr and drop_rec go together");
+  if (!has) return nullptr;
+  check_bf16(*dr, "dr"); check_contig(*dr, "dr");
+  TORCH_CHECK(dr->numel() == x.numel(), op, ": dr size");
+  return bpm(*dr);
 }
 
 void ln_backward_op(const Tensor& dy, const Tensor& x, const Tensor& g, const Tensor& mean,
                     const Tensor& rstd, const Tensor& dx, const Tensor& dg, const Tensor& db,
-                    const optional<Tensor>& addend) {
+                    const optional<Tensor>& addend, const optional<Tensor>& dr,
+                    const optional<Tensor>& drop_rec, int64_t drop_site, int64_t drop_thr, double drop_scale) {
   check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(dx, "dx");
   check_contig(dy, "dy"); check_contig(x, "x"); check_contig(dx, "dx");
   check_f32(dg, "dg"); check_f32(db, "db");
@@ -839,17 +872,21 @@ void ln_backward_op(const Tensor& dy, const Tensor& x, const Tensor& g, const Te
     add = bp(*addend);
   }
   const int64_t D = x.size(-1);
+  const tam::LnDrop drop = drop_args(drop_rec, drop_site, drop_thr, drop_scale, x, "tam.ln_backward");
+  tam::bf16_t* dres = ln_dres(dr, drop, x, "tam.ln_backward");
   Tensor ws = at::empty({(int64_t)tam::LN_MAX_BLOCKS * 2 * D}, x.options().dtype(at::kFloat));
   tam::ln_backward(bp(dy), bp(x), g.data_ptr<float>(), mean.data_ptr<float>(),
                    rstd.data_ptr<float>(), bpm(dx), add, dg.data_ptr<float>(), db.data_ptr<float>(),
-                   ws.data_ptr<float>(), x.numel() / D, (int)D, cur_stream(x));
+                   ws.data_ptr<float>(), x.numel() / D, (int)D, cur_stream(x), dres, drop);
 }
 
 // LN backward without its column reduce: per-block partials into ws (fp32,
 // >= LN_MAX_BLOCKS * 2D); returns the partial-row count for col_reduce_acc
 int64_t ln_backward_split_op(const Tensor& dy, const Tensor& x, const Tensor& g, const Tensor& mean,
                              const Tensor& rstd, const Tensor& dx, const Tensor& ws,
-                             const optional<Tensor>& addend) {
+                             const optional<Tensor>& addend, const optional<Tensor>& dr,
+                             const optional<Tensor>& drop_rec, int64_t drop_site, int64_t drop_thr,
+                             double drop_scale) {
   check_bf16(dy, "dy"); check_bf16(x, "x"); check_bf16(dx, "dx");
   check_contig(dy, "dy"); check_contig(x, "x"); check_contig(dx, "dx");
   check_f32(ws, "ws");
@@ -862,9 +899,28 @@ int64_t ln_backward_split_op(const Tensor& dy, const Tensor& x, const Tensor& g,
     TORCH_CHECK(addend->numel() == x.numel(), "tam.ln_backward_split: addend size");
     add = bp(*addend);
   }
+  const tam::LnDrop drop = drop_args(drop_rec, drop_site, drop_thr, drop_scale, x, "tam.ln_backward_split");
+  tam::bf16_t* dres = ln_dres(dr, drop, x, "tam.ln_backward_split");
   return tam::ln_backward_partial(bp(dy), bp(x), g.data_ptr<float>(), mean.data_ptr<float>(),
                                   rstd.data_ptr<float>(), bpm(dx), add, ws.data_ptr<float>(), x.numel() / D,
-                                  (int)D, cur_stream(x));
+                                  (int)D, cur_stream(x), dres, drop);
+}
+
+// training dropout, standalone (dropout.hip); y may be x. The backward is the
+// same op on dy
+void dropout_apply_op(const Tensor& x, const Tensor& y, const Tensor& rec, int64_t site, int64_t thr,
+                      double scale) {
+  check_bf16(x, "x"); check_bf16(y, "y"); check_contig(x, "x"); check_contig(y, "y");
+  TORCH_CHECK(y.numel() == x.numel() && y.device() == x.device(), "tam.dropout_apply: y must match x");
+  TORCH_CHECK((((uintptr_t)x.data_ptr()) & 15) == 0 && (((uintptr_t)y.data_ptr()) & 15) == 0,
+              "tam.dropout_apply: x and y must be 16-B aligned");
+  const tam::LnDrop d = drop_args(rec, site, thr, scale, x, "tam.dropout_apply");
+  tam::dropout_apply(bp(x), bpm(y), x.numel(), d.thr, d.scale, d.rec, (int)d.site, cur_stream(x));
+}
+void dropout_advance_op(const Tensor& rec) {
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kInt && rec.numel() >= 4 && rec.is_contiguous(),
+              "tam.dropout_advance: rec must be an int32 [4] GPU tensor");
+  tam::dropout_advance(rec.data_ptr<int>(), cur_stream(rec));
 }
 
 // out0[c] += sum_b part[b][c] (c < split), out1[c - split] += ... (c >= split)
@@ -1358,9 +1414,11 @@ TORCH_LIBRARY(tam, m) {
   m.def("wgrad_slab_reduce_many(Tensor[] slabs, int[] sp, Tensor(a!)[] dw, int[] mode) -> ()", &wgrad_slab_reduce_many_op);
   m.def("bn_forward(Tensor x, Tensor? res, Tensor(a!) y, Tensor gamma, Tensor beta, Tensor(b!)? run_mean, Tensor(c!)? run_var, Tensor(d!) save_mean, Tensor(e!) save_rstd, float eps, float momentum, bool relu, Tensor(f!)? sums=None, bool sums_ready=False, Tensor(g!)? ymask=None) -> ()", &bn_forward_op);
   m.def("bn_backward(Tensor dy, Tensor? y, Tensor x, Tensor mean, Tensor rstd, Tensor gamma, Tensor(a!) dx, Tensor(b!)? dres, Tensor(c!)? dgamma, Tensor(d!)? dbeta, bool relu, Tensor? addend=None, Tensor(e!)? sums=None, bool sums_ready=False, Tensor? ymask=None) -> ()", &bn_backward_op);
-  m.def("ln_forward(Tensor x, Tensor g, Tensor b, Tensor(a!) y, Tensor(b!) mean, Tensor(c!) rstd, float eps, Tensor? addend=None, Tensor(d!)? sum_out=None) -> ()", &ln_forward_op);
-  m.def("ln_backward(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) dg, Tensor(c!) db, Tensor? addend=None) -> ()", &ln_backward_op);
-  m.def("ln_backward_split(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) ws, Tensor? addend=None) -> int", &ln_backward_split_op);
+  m.def("ln_forward(Tensor x, Tensor g, Tensor b, Tensor(a!) y, Tensor(b!) mean, Tensor(c!) rstd, float eps, Tensor? addend=None, Tensor(d!)? sum_out=None, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &ln_forward_op);
+  m.def("ln_backward(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) dg, Tensor(c!) db, Tensor? addend=None, Tensor(d!)? dr=None, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &ln_backward_op);
+  m.def("ln_backward_split(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) ws, Tensor? addend=None, Tensor(c!)? dr=None, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> int", &ln_backward_split_op);
+  m.def("dropout_apply(Tensor x, Tensor(a!) y, Tensor rec, int site, int thr, float scale) -> ()", &dropout_apply_op);
+  m.def("dropout_advance(Tensor(a!) rec) -> ()", &dropout_advance_op);
   m.def("col_reduce_acc(Tensor part, int nblk, int W, Tensor(a!) out0, Tensor(b!) out1, int split) -> ()", &col_reduce_acc_op);
   m.def("col_reduce_acc_batch(Tensor[] parts, int[] nblk, Tensor(a!)[] out0, Tensor(b!)[] out1) -> ()", &col_reduce_acc_batch_op);
   m.def("maxpool_forward(Tensor x, Tensor(a!) y, Tensor(b!) idx, int R, int S, int stride, int pad) -> ()", &maxpool_forward_op);

@@ -56,18 +56,36 @@ void bn_backward(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const 
 // LayerNorm over last dim D (D % 8 == 0, D <= 2048)
 // addend (optional): LN of (x + addend), the bf16 sum also stored to sum_out
 // (a residual add fused into the next pre-LN)
+// drop (rec != nullptr, with addend): training dropout on the addend stream,
+// sum_out = x + drop(addend); the mask comes from (rec, site, thr) through
+// Philox (tam/philox.h) and is not stored
+struct LnDrop {
+  const int* rec = nullptr;   // the trainer's dropout record, int32[4] {seed, stream, step, 0}
+  unsigned site = 0;          // ordinal of the dropout call within the forward
+  unsigned thr = 0;           // round(p * 65536): kept iff u16 >= thr
+  float scale = 1.f;          // 65536 / (65536 - thr)
+};
 void ln_forward(const bf16_t* x, const float* g, const float* b, bf16_t* y, float* mean,
                 float* rstd, long rows, int D, float eps, hipStream_t s, const bf16_t* addend = nullptr,
-                bf16_t* sum_out = nullptr);
+                bf16_t* sum_out = nullptr, LnDrop drop = {});
 // dx = LN-backward(dy) (+ addend, the fused gradient of a skip connection)
+// dres + drop (both or neither): dres = keep ? dx * scale : 0, the gradient of
+// the branch ln_forward dropped out with the same (rec, site, thr)
 void ln_backward(const bf16_t* dy, const bf16_t* x, const float* g, const float* mean,
                  const float* rstd, bf16_t* dx, const bf16_t* addend, float* dg, float* db,
-                 float* ws, long rows, int D, hipStream_t s);
+                 float* ws, long rows, int D, hipStream_t s, bf16_t* dres = nullptr, LnDrop drop = {});
 // the same without the column reduce: per-block partial dgamma | dbeta rows
 // in ws; returns their count (col_reduce_acc finishes, e.g. on a side stream)
 int ln_backward_partial(const bf16_t* dy, const bf16_t* x, const float* g, const float* mean,
                         const float* rstd, bf16_t* dx, const bf16_t* addend, float* ws, long rows, int D,
-                        hipStream_t s);
+                        hipStream_t s, bf16_t* dres = nullptr, LnDrop drop = {});
+
+// training dropout, standalone (dropout.hip): y = keep ? bf16(x * scale) : +0
+// over n contiguous elements (16-B aligned; y == x allowed); the backward is
+// the same call on dy. dropout_advance: rec[2] += 1, one thread, once per step
+void dropout_apply(const bf16_t* x, bf16_t* y, long n, unsigned thr, float scale, const int* rec, int site,
+                   hipStream_t s);
+void dropout_advance(int* rec, hipStream_t s);
 
 // pooling
 void maxpool_forward(const bf16_t* x, bf16_t* y, uint8_t* idx, int N, int H, int W, int C, int P,

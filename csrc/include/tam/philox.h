@@ -1,0 +1,67 @@
+// tiresias_amd — Philox4x32-10 counter-based generator and the dropout mask
+// built on it (device and host, plain C++: a 32x32->64 multiply is all it
+// needs).
+//
+// Mask contract (README "Training dropout"; tests rebuild it on the host):
+// one Philox call per group of 8 consecutive elements of a contiguous tensor.
+// For flat element index i: q = i >> 3, j = i & 7,
+//   counter = (q & 0xffffffff, q >> 32, site, step), key = (seed, stream),
+//   u = (out[j >> 1] >> (16 * (j & 1))) & 0xffff, kept iff u >= thr,
+// thr = round(p * 65536) in (0, 65536). Kept elements are scaled by
+// fp32(65536) / fp32(65536 - thr), dropped ones become +0. Nothing is stored:
+// the backward regenerates the mask from the same (record, site).
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define TAM_HD __host__ __device__ __forceinline__
+#else
+#define TAM_HD inline
+#endif
+
+namespace tam {
+
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u;
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
+
+TAM_HD void philox4x32_10(const uint32_t (&ctr)[4], const uint32_t (&key)[2], uint32_t (&out)[4]) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
+  uint32_t k0 = key[0], k1 = key[1];
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)kPhiloxM0 * c0;
+    const uint64_t p1 = (uint64_t)kPhiloxM1 * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += kPhiloxW0;
+    k1 += kPhiloxW1;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// the dropout record a trainer keeps on the device: int32[4] {seed, stream,
+// step, 0}; dropout_advance bumps step once per training step
+struct DropRec {
+  uint32_t seed, stream, step;
+};
+
+// keep bits of group q (elements 8q .. 8q+7): bit j set = element 8q+j is kept
+TAM_HD uint32_t drop_keep8(uint64_t q, uint32_t site, const DropRec& r, uint32_t thr) {
+  const uint32_t ctr[4] = {(uint32_t)q, (uint32_t)(q >> 32), site, r.step};
+  const uint32_t key[2] = {r.seed, r.stream};
+  uint32_t o[4];
+  philox4x32_10(ctr, key, o);
+  uint32_t bits = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    bits |= ((o[i] & 0xffffu) >= thr ? 1u : 0u) << (2 * i);
+    bits |= ((o[i] >> 16) >= thr ? 1u : 0u) << (2 * i + 1);
+  }
+  return bits;
+}
+
+}  // namespace tam

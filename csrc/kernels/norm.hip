@@ -9,6 +9,7 @@
 // producing dx (and the residual-branch gradient) plus dgamma/dbeta.
 #include "tam/common.h"
 #include "tam/kernels.h"
+#include "tam/philox.h"
 
 namespace tam {
 
@@ -647,7 +648,11 @@ void bn_backward(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const 
 
 // ---------------------------------------------------------------- LayerNorm
 // One wave per row; D <= 64*8*ROWVEC. Vectorized 8 bf16 per lane-step.
-template <int VEC>
+// DROP: training dropout on the addend stream, s = x + drop(addend): the mask
+// of the 8 elements a lane-step holds is one Philox call (tam/philox.h) on
+// their flat group index; nothing is stored, ln_bwd_kernel regenerates it.
+// DROP = false is the kernel as it was (same code, same bits).
+template <int VEC, bool DROP>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(const bf16_t* __restrict__ x,
                                                       const float* __restrict__ g,
                                                       const float* __restrict__ b,
@@ -655,11 +660,13 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const bf16_t* __restrict__ 
                                                       float* __restrict__ mean_o,
                                                       float* __restrict__ rstd_o, long rows, int D,
                                                       float eps, const bf16_t* __restrict__ addend,
-                                                      bf16_t* __restrict__ sum_out) {
+                                                      bf16_t* __restrict__ sum_out, LnDrop drop) {
   const int lane = threadIdx.x & 63;
   const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
   if (row >= rows) return;
   const bf16_t* xr = x + row * D;
+  DropRec dr{};
+  if (DROP) dr = DropRec{(uint32_t)drop.rec[0], (uint32_t)drop.rec[1], (uint32_t)drop.rec[2]};
   float f[VEC][8];
   float s = 0.f;
 #pragma unroll
@@ -672,8 +679,21 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const bf16_t* __restrict__ 
         // residual stream) and normalised -- as an add pass + LN would see it
         float a[8];
         unpack8(*(const uint4*)(addend + row * D + c), a);
+        if (DROP) {
+          // a dropped position keeps x untouched (its bits, -0 included); a
+          // kept one adds the fp32-rounded product (no fused multiply-add, so
+          // the host mirror rounds the same way)
+          const uint32_t keep = drop_keep8((uint64_t)(row * D + c) >> 3, drop.site, dr, drop.thr);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[v][j] += a[j];
+          for (int j = 0; j < 8; ++j) {
+#pragma clang fp contract(off)
+            const float t = a[j] * drop.scale;
+            if ((keep >> j) & 1u) f[v][j] += t;
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[v][j] += a[j];
+        }
         const uint4 pk = pack8(f[v]);
         *(uint4*)(sum_out + row * D + c) = pk;
         unpack8(pk, f[v]);
@@ -709,7 +729,10 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const bf16_t* __restrict__ 
   }
 }
 
-template <int VEC>
+// DROP: second output dr = keep ? dx * scale : +0, the gradient of the
+// dropped-out residual branch of ln_fwd_kernel<.., true>, from the dx this
+// kernel already holds in registers (one more 16-B store per lane-step).
+template <int VEC, bool DROP>
 __global__ void __launch_bounds__(256) ln_bwd_kernel(const bf16_t* __restrict__ dy,
                                                       const bf16_t* __restrict__ x,
                                                       const float* __restrict__ g,
@@ -718,7 +741,8 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const bf16_t* __restrict__ 
                                                       bf16_t* __restrict__ dx,
                                                       const bf16_t* __restrict__ addend,
                                                       float* __restrict__ part, long rows,
-                                                      int D, int rows_per_block) {
+                                                      int D, int rows_per_block,
+                                                      bf16_t* __restrict__ dres, LnDrop drop) {
   // each wave processes rows_per_block/4 rows, accumulating dgamma/dbeta in
   // registers; the 4 waves combine through LDS and the block writes ONE
   // partial row [2*D] (no atomics; a column-reduce kernel finishes).
@@ -730,6 +754,8 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const bf16_t* __restrict__ 
   for (int v = 0; v < VEC; ++v)
 #pragma unroll
     for (int j = 0; j < 8; ++j) dgacc[v][j] = dbacc[v][j] = 0.f;
+  DropRec dr{};
+  if (DROP) dr = DropRec{(uint32_t)drop.rec[0], (uint32_t)drop.rec[1], (uint32_t)drop.rec[2]};
   const long r0 = (long)blockIdx.x * rows_per_block;
   for (long row = r0 + w; row < min(rows, r0 + rows_per_block); row += 4) {
     const float mu = mean[row], rs = rstd[row];
@@ -769,6 +795,12 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const bf16_t* __restrict__ 
           for (int j = 0; j < 8; ++j) o[j] += a[j];
         }
         *(uint4*)(dx + row * D + c) = pack8(o);
+        if (DROP) {
+          const uint32_t keep = drop_keep8((uint64_t)(row * D + c) >> 3, drop.site, dr, drop.thr);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o[j] = (keep >> j) & 1u ? o[j] * drop.scale : 0.f;
+          *(uint4*)(dres + row * D + c) = pack8(o);
+        }
       }
     }
   }
@@ -796,31 +828,51 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const bf16_t* __restrict__ 
 
 void ln_forward(const bf16_t* x, const float* g, const float* b, bf16_t* y, float* mean,
                 float* rstd, long rows, int D, float eps, hipStream_t s, const bf16_t* addend,
-                bf16_t* sum_out) {
+                bf16_t* sum_out, LnDrop drop) {
   const int blocks = (int)((rows + 3) / 4);
-  if (D <= 512) hipLaunchKernelGGL(ln_fwd_kernel<1>, dim3(blocks), dim3(256), 0, s, x, g, b, y, mean, rstd, rows, D, eps, addend, sum_out);
-  else if (D <= 1024) hipLaunchKernelGGL(ln_fwd_kernel<2>, dim3(blocks), dim3(256), 0, s, x, g, b, y, mean, rstd, rows, D, eps, addend, sum_out);
-  else hipLaunchKernelGGL(ln_fwd_kernel<4>, dim3(blocks), dim3(256), 0, s, x, g, b, y, mean, rstd, rows, D, eps, addend, sum_out);
+#define TAM_LN_FWD(V, DR) \
+  hipLaunchKernelGGL((ln_fwd_kernel<V, DR>), dim3(blocks), dim3(256), 0, s, x, g, b, y, mean, rstd, rows, D, eps, \
+                     addend, sum_out, drop)
+  if (drop.rec && addend) {
+    if (D <= 512) TAM_LN_FWD(1, true);
+    else if (D <= 1024) TAM_LN_FWD(2, true);
+    else TAM_LN_FWD(4, true);
+  } else {
+    if (D <= 512) TAM_LN_FWD(1, false);
+    else if (D <= 1024) TAM_LN_FWD(2, false);
+    else TAM_LN_FWD(4, false);
+  }
+#undef TAM_LN_FWD
 }
 
 int ln_backward_partial(const bf16_t* dy, const bf16_t* x, const float* g, const float* mean,
                         const float* rstd, bf16_t* dx, const bf16_t* addend, float* ws, long rows, int D,
-                        hipStream_t s) {
+                        hipStream_t s, bf16_t* dres, LnDrop drop) {
   // ws: LN_MAX_BLOCKS * 2 * D floats of per-block partial dgamma / dbeta
   int rpb = (int)((rows + LN_MAX_BLOCKS - 1) / LN_MAX_BLOCKS);
   rpb = ((rpb + 3) / 4) * 4;
   if (rpb < 8) rpb = 8;
   const int blocks = (int)((rows + rpb - 1) / rpb);
-  if (D <= 512) hipLaunchKernelGGL(ln_bwd_kernel<1>, dim3(blocks), dim3(256), 0, s, dy, x, g, mean, rstd, dx, addend, ws, rows, D, rpb);
-  else if (D <= 1024) hipLaunchKernelGGL(ln_bwd_kernel<2>, dim3(blocks), dim3(256), 0, s, dy, x, g, mean, rstd, dx, addend, ws, rows, D, rpb);
-  else hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(blocks), dim3(256), 0, s, dy, x, g, mean, rstd, dx, addend, ws, rows, D, rpb);
+#define TAM_LN_BWD(V, DR) \
+  hipLaunchKernelGGL((ln_bwd_kernel<V, DR>), dim3(blocks), dim3(256), 0, s, dy, x, g, mean, rstd, dx, addend, ws, \
+                     rows, D, rpb, dres, drop)
+  if (drop.rec && dres) {
+    if (D <= 512) TAM_LN_BWD(1, true);
+    else if (D <= 1024) TAM_LN_BWD(2, true);
+    else TAM_LN_BWD(4, true);
+  } else {
+    if (D <= 512) TAM_LN_BWD(1, false);
+    else if (D <= 1024) TAM_LN_BWD(2, false);
+    else TAM_LN_BWD(4, false);
+  }
+#undef TAM_LN_BWD
   return blocks;
 }
 
 void ln_backward(const bf16_t* dy, const bf16_t* x, const float* g, const float* mean,
                  const float* rstd, bf16_t* dx, const bf16_t* addend, float* dg, float* db,
-                 float* ws, long rows, int D, hipStream_t s) {
-  const int blocks = ln_backward_partial(dy, x, g, mean, rstd, dx, addend, ws, rows, D, s);
+                 float* ws, long rows, int D, hipStream_t s, bf16_t* dres, LnDrop drop) {
+  const int blocks = ln_backward_partial(dy, x, g, mean, rstd, dx, addend, ws, rows, D, s, dres, drop);
   col_reduce_acc(ws, blocks, 2 * D, dg, db, D, s);
 }
 

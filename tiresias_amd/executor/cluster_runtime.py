@@ -147,6 +147,7 @@ class ReplayJob:
     iterations: int
     batch: Optional[int] = None
     grad_clip: Optional[float] = None    # global-norm gradient clip of the job (None = off)
+    dropout: Optional[float] = None      # training dropout of the job (None = off)
 
 
 class Controller:
@@ -508,7 +509,7 @@ class Controller:
         now = self.now()
         for req in self.spool.poll():
             try:
-                jid, model, g, iters, batch, clip = self._validate(req)
+                jid, model, g, iters, batch, clip, drop = self._validate(req)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -520,7 +521,8 @@ class Controller:
                 continue
             spec = JobSpec(job_id=jid, submit_time=now, duration=iters * self._iter_est(model, g),
                            num_gpu=g, model=model, iterations=iters)
-            self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip)
+            self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
+                                        dropout=drop)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -529,7 +531,8 @@ class Controller:
 
     def _validate(self, req: dict):
         """Untrusted spool request -> (job_id, model, num_gpu, iterations,
-        batch, grad_clip); raises ValueError with the rejection reason."""
+        batch, grad_clip, dropout); raises ValueError with the rejection
+        reason."""
         from ..models import MODELS
 
         jid = req.get("job_id")
@@ -569,7 +572,13 @@ class Controller:
             clip = float(clip)
             if self.ddp_shard and g > 1:
                 raise ValueError("grad_clip is not supported for a multi-GPU job under ddp_shard")
-        return jid, model, g, iters, batch, clip
+        drop = req.get("dropout")
+        if drop is not None:
+            if (isinstance(drop, bool) or not isinstance(drop, (int, float)) or not 0 <= drop < 1
+                    or round(drop * 65536) >= 65536):
+                raise ValueError(f"dropout must be a number p with 0 <= p < 1 (quantised to 1/65536), got {drop!r}")
+            drop = float(drop)
+        return jid, model, g, iters, batch, clip, drop
 
     def status(self) -> dict:
         s = self.sched
@@ -630,7 +639,8 @@ class Controller:
                 rj = self.rjobs[j.job_id]
                 act = {"op": "start", "job": j.job_id, "ranks": ranks, "model": rj.model,
                        "iters": max(0, rj.iterations - self.done_iters[j.job_id]),
-                       "batch": rj.batch, "grad_clip": rj.grad_clip, "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
+                       "batch": rj.batch, "grad_clip": rj.grad_clip, "dropout": rj.dropout,
+                       "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
                     act["source"] = "snapshot"
@@ -883,13 +893,14 @@ class Worker:
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
+            t.set_dropout(act.get("dropout"))        # likewise (a change re-captures the graph)
             self._bind(t, ranks)
             if want and not t.use_graph and t.ddp is None:
                 t.enable_graph()
             return t
         t = Trainer(act["model"], self.device, batch=act.get("batch"), group=self._group(ranks),
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
-                    ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"))
+                    ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"))
         t.pool_key = key
         return t
 

@@ -19,7 +19,7 @@ from ..ops import _lib
 from ..ops import functional as Fx
 from ..ops.arena import Arena
 from ..parallel.ddp import GradBucketer
-from ..parallel.gang import comm_size
+from ..parallel.gang import comm_rank, comm_size
 
 
 class Trainer:
@@ -27,9 +27,12 @@ class Trainer:
                  data_seed: Optional[int] = None, use_graph: bool = False, bucket_mb: float = 32.0,
                  model_kwargs: Optional[dict] = None, lr: Optional[float] = None,
                  overlap_wgrad: Optional[bool] = None, branches: Optional[bool] = None,
-                 ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None):
+                 ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
+                 dropout: Optional[float] = None):
         self.model_name = model
         self.spec = MODELS[model]
+        if dropout is None:
+            dropout = self.spec.dropout
         if grad_clip is None:
             grad_clip = self.spec.clip
         if grad_clip is not None and ddp_shard and group is not None and comm_size(group) > 1:
@@ -39,6 +42,7 @@ class Trainer:
         if self.device.type == "cuda":
             _lib.load(required=True)
         self.batch = batch or self.spec.batch
+        self.seed = seed
         self.arena = Arena(self.device, seed=seed)
         self.model = make_model(model, self.arena, **(model_kwargs or {}))
         self.arena.materialize()
@@ -89,6 +93,12 @@ class Trainer:
         self._clip_part = None          # grad_sumsq's per-block fp64 partials
         self._clip_host = [1.0, 0.0, 0, 0]   # the same four words on the CPU path
         self.set_grad_clip(grad_clip)
+        # training dropout (set_dropout); None = off, nothing allocated or
+        # launched
+        self.dropout: Optional[float] = None
+        self._drop_rec = None           # int32[4] {seed, stream, step, 0} on the trainer's device
+        self._drop_at = None            # (seed, stream, step) the record holds, tracked on the host
+        self.set_dropout(dropout)
         # weight init and the synthetic batch were queued on the stream that
         # built the trainer; a step issued from another stream (GPU sharing
         # runs each job on its own stream) must wait for them first
@@ -122,6 +132,8 @@ class Trainer:
             # (an early flush on a side stream measured slower: ResNet-50 9.07
             # vs 8.89 ms, Transformer 5.41 vs 5.30; removed in round 6)
             Fx.defer_wgrad(True)
+        drop = self._drop_rec if self.dropout else None
+        Fx.set_dropout(drop)            # restarts the site ordinals of this forward
         try:
             if self.spec.kind == "image":
                 logits = self.model.forward(d["x"])
@@ -142,12 +154,62 @@ class Trainer:
                 Fx.defer_wgrad(False, discard=True)
             Fx.set_wgrad_stream(None)
             Fx.set_branch_streams(None)
+            Fx.set_dropout(None)
         if ws is not None:
             torch.cuda.current_stream(self.device).wait_stream(ws)   # join before the optimizer
         if self.device.type == "cuda" and self.ddp is None and nb:
             for s in self._bs:
                 torch.cuda.current_stream(self.device).wait_stream(s)
+        if drop is not None:
+            # the record's step word advances on the device, after every
+            # kernel that read it (the side streams are joined above): last
+            # launch of the forward + backward, inside a capture, so a graph
+            # replay draws fresh masks with no host write
+            if drop.is_cuda:
+                _lib.ops().dropout_advance(drop)
+            else:
+                drop[2] += 1
         return loss
+
+    # ------------------------------------------------------------ dropout
+    def set_dropout(self, p: Optional[float]) -> None:
+        """Training dropout with probability ``p`` at the model's dropout
+        sites (models/*.py; ``None`` or 0 turns it off, and then nothing is
+        allocated or launched). ``p`` is quantised to 1/65536. Masks are not
+        stored: forward and backward kernels derive them from this trainer's
+        device record {seed, stream, step} (ops/functional.py "dropout"),
+        ``stream`` being the member's position in its gang, so DDP members
+        draw different masks. The record advances on the device once per
+        step; the host rewrites it only when (seed, stream, step_count)
+        change other than by a step (``_drop_sync``), so a resumed or migrated
+        job continues the same mask sequence. A change of ``p`` re-captures
+        the step graph."""
+        if p is not None:
+            p = float(p)
+            if Fx.dropout_threshold(p) == 0 or not hasattr(self.model, "dropout"):
+                p = None            # (a model without dropout sites ignores it)
+        if p != self.dropout:
+            self._graph = None
+            self._g_loss = None
+        self.dropout = p
+        if hasattr(self.model, "dropout"):
+            self.model.dropout = p or 0.0
+        if p is not None and self._drop_rec is None:
+            self._drop_rec = torch.zeros(4, dtype=torch.int32, device=self.device)
+            self._drop_at = None
+
+    def _drop_sync(self) -> None:
+        """Before a step: make the record hold (seed, gang position,
+        step_count). A host compare per step; a write only after
+        construction, ``reset``, a restore / P2P receive that set
+        ``step_count``, or a ``rebind`` to another gang position."""
+        if not self.dropout:
+            return
+        want = (int(self.seed) & 0xFFFFFFFF, comm_rank(self.group) & 0xFFFFFFFF, int(self.step_count) & 0xFFFFFFFF)
+        if want != self._drop_at:
+            i32 = [((v ^ 0x80000000) - 0x80000000) for v in want]       # the words as int32
+            self._drop_rec.copy_(torch.tensor(i32 + [0], dtype=torch.int32))
+            self._drop_at = want
 
     # ------------------------------------------------------------ gradient clip
     def set_grad_clip(self, v: Optional[float]) -> None:
@@ -352,6 +414,10 @@ class Trainer:
         if self._ready is not None:
             torch.cuda.current_stream(self.device).wait_event(self._ready)
             self._ready = None
+        self._drop_sync()
+        if self._drop_at is not None and self.dropout:
+            # what the record holds once this step's advance has run
+            self._drop_at = self._drop_at[:2] + ((self._drop_at[2] + 1) & 0xFFFFFFFF,)
         if self.use_graph and self._graph is None and self._warm < 2:
             # the first two steps are REAL steps run eagerly on a side stream
             # (allocator pools, library handles/workspaces, GEMM route tuning
@@ -570,6 +636,7 @@ class Trainer:
         for k, v in fresh.items():
             self.data[k].copy_(v)
         self.step_count = 0
+        self.seed = seed
         self.last_loss = None
         if self._clip is not None:
             self._clip.zero_()

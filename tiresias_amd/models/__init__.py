@@ -45,6 +45,10 @@ class ModelSpec:
     # global-norm gradient clip of the job's recipe (executor/trainer.py);
     # None = off. No shipped model sets it: a job asks for it (--grad-clip)
     clip: Optional[float] = None
+    # training dropout of the job's recipe at the model's dropout sites
+    # (Trainer.set_dropout); None = off. No shipped model sets it: a job asks
+    # for it (--dropout)
+    dropout: Optional[float] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

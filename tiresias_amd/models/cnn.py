@@ -147,14 +147,18 @@ VGG16_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512, "M",
 
 
 class VGG16:
-    """VGG-16 (configuration D), NHWC, conv+bias+ReLU fused; no dropout
-    (synthetic-data throughput workload)."""
+    """VGG-16 (configuration D), NHWC, conv+bias+ReLU fused. ``dropout=p``
+    (off by default; the recipe's 0.5) drops the fc6 and fc7 ReLU outputs
+    through ``Fx.dropout`` (masks regenerated in the backward, never stored).
+    The consumer's ``in_relu`` input-gradient mask (input > 0) stays correct:
+    a dropped element is 0 and its gradient is zero anyway."""
 
     name = "vgg16"
 
     def __init__(self, arena: Arena, num_classes: int = 1000, cfg=VGG16_CFG, in_ch: int = 8,
-                 image: int = 224, fc: int = 4096):
+                 image: int = 224, fc: int = 4096, dropout: float = 0.0):
         self.arena = arena
+        self.dropout = dropout
         A = arena
         self.layers: List[Tuple[str, object]] = []
         cin = in_ch
@@ -198,8 +202,9 @@ class VGG16:
             in_relu = True
         y = y.reshape(y.shape[0], -1)
         (w0, b0), (w1, b1), (w2, b2) = self.fc
-        y = Fx.linear(y, w0, b0, relu=True, in_relu=True, mask_own_relu=False)
-        y = Fx.linear(y, w1, b1, relu=True, in_relu=True, mask_own_relu=False)
+        p = self.dropout if (self.training and self.dropout and self.dropout > 0) else None
+        y = Fx.dropout(Fx.linear(y, w0, b0, relu=True, in_relu=True, mask_own_relu=False), p)
+        y = Fx.dropout(Fx.linear(y, w1, b1, relu=True, in_relu=True, mask_own_relu=False), p)
         return Fx.linear(y, w2, b2, in_relu=True)
 
     def buffers(self):

@@ -18,6 +18,11 @@ The LSTM layer is one autograd Function over the whole sequence:
 The per-step loop is launch-bound; on MI355X both recurrences run as ONE
 persistent kernel per layer-direction (lstm.hip, grid barrier per timestep,
 W_hh slices resident in VGPRs), the per-step path remaining the fallback.
+
+Dropout (``dropout=p``, off by default; the recipe's 0.2) is applied to the
+input of every LSTM layer after the first, encoder and decoder, through
+``Fx.dropout`` before the input projection; the recurrence kernels are not
+touched, and the masks are regenerated in the backward, never stored.
 """
 from __future__ import annotations
 
@@ -315,8 +320,9 @@ class GNMT:
     shared = False
 
     def __init__(self, arena: Arena, vocab: int = 32000, hidden: int = 1024, enc_layers: int = 4,
-                 dec_layers: int = 4, heads: int = 16):
+                 dec_layers: int = 4, heads: int = 16, dropout: float = 0.0):
         assert hidden == heads * 64
+        self.dropout = dropout
         A = arena
         H = hidden
         self.arena, self.H, self.heads, self.vocab = arena, H, heads, vocab
@@ -347,6 +353,7 @@ class GNMT:
 
     def forward(self, batch):
         src, tgt_in = batch["src"], batch["tgt_in"]       # [B,S] token ids
+        pd = self.dropout if (self.training and self.dropout and self.dropout > 0) else None
         if src.is_cuda and PERSIST and self.persist and not self.shared:
             # the sync words of every persistent launch of this step (forward
             # and backward of each layer-direction) zeroed by one fill instead
@@ -384,10 +391,10 @@ class GNMT:
             bw = lstm(xb, self.enc[1], reverse=True, model=self)
         fw = lstm(x, self.enc[0], model=self)
         bw = Fx.join_branch(0, bw)
-        h = lstm(Fx.cat2(fw, bw), self.enc[2], model=self)
+        h = lstm(Fx.dropout(Fx.cat2(fw, bw), pd), self.enc[2], model=self)
         for p in self.enc[3:]:                           # residual from layer 3 on
             hi, h = Fx.fanout(h, 2)
-            h = Fx.add(h, lstm(hi, p, model=self))
+            h = Fx.add(h, lstm(Fx.dropout(hi, pd), p, model=self))
         kv = Fx.linear(h, self.att_kv)                   # [S,B,2H]
         d0, q = Fx.join_branch(1, d0, q)
         ctxv = Fx.cross_attention(q, kv, self.heads, time_major=True)   # [T,B,H]
@@ -396,9 +403,9 @@ class GNMT:
         for i, p in enumerate(self.dec[1:]):
             if i >= 1:
                 hi, h = Fx.fanout(h, 2)
-                h = Fx.add(h, lstm(Fx.cat2(hi, cs[i]), p, model=self))
+                h = Fx.add(h, lstm(Fx.dropout(Fx.cat2(hi, cs[i]), pd), p, model=self))
             else:
-                h = lstm(Fx.cat2(h, cs[i]), p, model=self)
+                h = lstm(Fx.dropout(Fx.cat2(h, cs[i]), pd), p, model=self)
         out = Fx.cat2(h, cs[-1])                         # [T,B,2H]
         return Fx.linear(out, self.cls_w, self.cls_b)    # [T,B,V] (logits_time_major)
 

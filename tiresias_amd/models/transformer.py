@@ -12,7 +12,13 @@ MI355X-first layout decisions:
     and the ReLU backward into the second GEMM's dgrad epilogue;
   * tied source/target embedding + output projection; the loss is the fused
     softmax-xent kernel with label smoothing 0.1.
-Dropout is omitted (synthetic-data throughput workload).
+Dropout (``dropout=p``, off by default; the paper's P_drop = 0.1): every
+sub-layer output -- each pending residual, the ones the final ``enc_ln`` /
+``dec_ln`` add included -- is dropped out inside the fused add + LayerNorm
+kernels, and the two embedded inputs through the standalone kernel. Masks are
+regenerated in the backward, never stored (ops/functional.py "dropout").
+Attention-probability dropout is out of scope: the paper's P_drop does not
+include it, and it would need changes to the attention kernels.
 """
 from __future__ import annotations
 
@@ -28,7 +34,8 @@ class TransformerBase:
     name = "transformer"
 
     def __init__(self, arena: Arena, vocab: int = 32000, d: int = 512, heads: int = 8,
-                 ffn: int = 2048, enc_layers: int = 6, dec_layers: int = 6, max_len: int = 1024):
+                 ffn: int = 2048, enc_layers: int = 6, dec_layers: int = 6, max_len: int = 1024,
+                 dropout: float = 0.0):
         assert d == heads * 64, "kernels are built for head_dim 64"
         A = arena
         self.arena, self.d, self.h, self.vocab = arena, d, heads, vocab
@@ -66,6 +73,11 @@ class TransformerBase:
                        A.add("dec.kv.b", (dec_layers * 2 * d,), init="zeros", decay=False))
         self.dec_ln = ln("dec.ln")
         self.training = True
+        self.dropout = dropout
+
+    @property
+    def _p(self):
+        return self.dropout if (self.training and self.dropout and self.dropout > 0) else None
 
     @staticmethod
     def _sinusoid(n, d, dev):
@@ -79,15 +91,17 @@ class TransformerBase:
 
     def _embed(self, ids):
         # scale + positional table in the embedding kernel (no broadcast copy)
-        return Fx.embedding(ids, self.emb, scale=math.sqrt(self.d), pos=self.pos[:ids.shape[1]])
+        return Fx.dropout(Fx.embedding(ids, self.emb, scale=math.sqrt(self.d), pos=self.pos[:ids.shape[1]]),
+                          self._p)
 
-    @staticmethod
-    def _ln_skip(x, r, p):
-        """(x + r, LN(x + r)) with the residual add fused into the LN kernel,
-        or (x, LN(x)) when no residual is pending."""
+    def _ln_skip(self, x, r, p):
+        """(x + r, LN(x + r)) with the residual add (and the dropout of r)
+        fused into the LN kernel, or (x, LN(x)) when no residual is pending."""
         if r is None:
             return Fx.layernorm_skip(x, *p)
-        return Fx.add_layernorm_skip(x, r, *p)
+        if self._p is None:
+            return Fx.add_layernorm_skip(x, r, *p)
+        return Fx.add_layernorm_skip(x, r, *p, drop=self._p)
 
     def _ffn(self, x, r, L):
         """FFN sub-block: returns (residual stream, pending FFN output)."""

@@ -761,6 +761,137 @@ def batchnorm(x: torch.Tensor, g: Param, b: Param, run_mean: Optional[torch.Tens
     return y
 
 
+# ============================================================ dropout
+# Training dropout without stored masks: the mask of a dropout call is a pure
+# function of the trainer's dropout record (int32[4] {seed, stream, step, 0},
+# on the data's device), the call's ordinal within the forward (its site) and
+# the flat element index, through Philox4x32-10 (csrc/include/tam/philox.h).
+# The forward generates it, the backward regenerates it. One Philox call
+# covers 8 consecutive elements: for element i, q = i >> 3 and j = i & 7, the
+# counter is (q & 0xffffffff, q >> 32, site, step), the key (seed, stream), and
+# u = (out[j >> 1] >> (16 * (j & 1))) & 0xffff; the element is kept iff
+# u >= thr with thr = round(p * 65536), and kept elements are scaled by
+# fp32(65536) / fp32(65536 - thr). The step word advances on the device
+# (dropout_advance, last launch of the trainer's forward + backward), so a
+# hipGraph replay draws fresh masks with no host write. The CPU path builds
+# the same mask in torch: a CPU trainer drops what a GPU trainer drops.
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 over int64 tensors holding 32-bit words (any of c0..c3
+    may be a Python int when another is a tensor); returns the 4 output words."""
+    for _ in range(10):
+        p0 = c0 * _PHILOX_M0          # wraps to the low 64 bits, which is the product
+        p1 = c2 * _PHILOX_M1
+        n0 = ((p1 >> 32) & _M32) ^ c1 ^ k0
+        n2 = ((p0 >> 32) & _M32) ^ c3 ^ k1
+        c1, c3 = p1 & _M32, p0 & _M32
+        c0, c2 = n0, n2
+        k0, k1 = (k0 + _PHILOX_W0) & _M32, (k1 + _PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def dropout_threshold(p: float) -> int:
+    """thr = round(p * 65536): p is quantised to 1/65536; 0 means no dropout."""
+    p = float(p)
+    thr = int(round(p * 65536.0)) if p == p else -1
+    if not (0.0 <= p < 1.0 and 0 <= thr < 65536):
+        raise ValueError(f"dropout must satisfy 0 <= p < 1 with round(p * 65536) < 65536, got {p}")
+    return thr
+
+
+def dropout_scale(thr: int) -> float:
+    """fp32(65536) / fp32(65536 - thr), one fp32 division, as a Python float."""
+    return float(torch.tensor(65536.0, dtype=torch.float32) / torch.tensor(float(65536 - thr), dtype=torch.float32))
+
+
+def dropout_mask(n: int, site: int, seed: int, stream: int, step: int, thr: int) -> torch.Tensor:
+    """Keep mask (bool [n], CPU) of a dropout call over n contiguous elements."""
+    ng = (n + 7) // 8
+    q = torch.arange(ng, dtype=torch.int64)
+    c0 = q & _M32
+    c1 = q >> 32
+    o = philox4x32_10(c0, c1, torch.full_like(q, site & _M32), torch.full_like(q, step & _M32),
+                      seed & _M32, stream & _M32)
+    w = torch.stack(o, 1)                                       # [ng, 4]
+    u = torch.stack([w & 0xFFFF, (w >> 16) & 0xFFFF], 2)        # [ng, 4, 2]: element j = 2 * word + half
+    return u.reshape(-1)[:n] >= thr
+
+
+_DROP_REC: Optional[torch.Tensor] = None
+_DROP_SITE = 0
+
+
+def set_dropout(rec: Optional[torch.Tensor]) -> None:
+    """Install a trainer's dropout record for the forward + backward that
+    follows (None: dropout calls are the identity) and restart the site
+    ordinals. The trainer does this at the start of every ``_fwd_bwd``."""
+    global _DROP_REC, _DROP_SITE
+    _DROP_REC = rec
+    _DROP_SITE = 0
+
+
+def _drop_args(p: Optional[float]):
+    """(rec, site, thr, scale) of the next dropout call, or None when the call
+    is the identity (p None / 0 / below 1/131072, or no record installed)."""
+    global _DROP_SITE
+    if p is None or _DROP_REC is None or not p:
+        return None
+    thr = dropout_threshold(p)
+    if thr == 0:
+        return None
+    site = _DROP_SITE
+    _DROP_SITE += 1
+    return (_DROP_REC, site, thr, dropout_scale(thr))
+
+
+def _cpu_keep(x: torch.Tensor, drop) -> torch.Tensor:
+    rec, site, thr, _ = drop
+    seed, stream, step = (int(v) for v in rec[:3].tolist())
+    return dropout_mask(x.numel(), site, seed, stream, step, thr).view(x.shape)
+
+
+def _dropout_apply(x: torch.Tensor, drop) -> torch.Tensor:
+    rec, site, thr, scale = drop
+    if x.is_cuda:
+        if x.data_ptr() & 15:
+            x = x.clone()
+        y = torch.empty_like(x)
+        _T().dropout_apply(x, y, rec, site, thr, scale)
+        return y
+    sc = torch.tensor(scale, dtype=torch.float32)
+    return torch.where(_cpu_keep(x, drop), (x.float() * sc).to(BF16), torch.zeros((), dtype=BF16))
+
+
+class _Dropout(Function):
+    """y = keep ? bf16(x * scale) : +0; the backward is the same kernel on dy
+    with the mask regenerated from (record, site)."""
+
+    @staticmethod
+    def forward(ctx, x, drop):
+        ctx.drop = drop
+        return _dropout_apply(x, drop)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _dropout_apply(dy.contiguous(), ctx.drop), None
+
+
+def dropout(x: torch.Tensor, p: Optional[float]) -> torch.Tensor:
+    """Training dropout with probability p (quantised to 1/65536). Returns x
+    itself, launching nothing, when p is None / 0 or no record is installed
+    (``set_dropout``)."""
+    drop = _drop_args(p)
+    if drop is None:
+        return x
+    if not x.is_contiguous():
+        x = x.contiguous()
+    return _Dropout.apply(x, drop)
+
+
 # ============================================================ LayerNorm
 # (a side-stream column reduce of the LN weight gradients beside the next
 # input-gradient GEMM measured much slower in hipGraph replay -- Transformer
@@ -779,16 +910,18 @@ _DEFER_LNRED: list = []
 # round 6)
 
 
-def _ln_backward(dy, x, g: Param, b: Param, mean, rstd, dx, addend=None) -> bool:
+def _ln_backward(dy, x, g: Param, b: Param, mean, rstd, dx, addend=None, dr=None, drop=None) -> bool:
     """LN backward; returns True when dgamma / dbeta were deferred to the
-    flush (their grad_ready() then comes from flush_wgrad)."""
+    flush (their grad_ready() then comes from flush_wgrad). dr + drop: the
+    kernel also writes dr = keep ? dx * scale : 0 (see _AddLNSkip)."""
     deferred = _DEFER_WGRAD is not None and LN_DEFER
+    extra = () if drop is None else (dr,) + tuple(drop)
     if not deferred:
-        _T().ln_backward(dy, x, g.master, mean, rstd, dx, g.grad, b.grad, addend)
+        _T().ln_backward(dy, x, g.master, mean, rstd, dx, g.grad, b.grad, addend, *extra)
         return False
     D = x.shape[-1]
     ws = torch.empty(_LN_MAX_BLOCKS * 2 * D, dtype=torch.float32, device=x.device)
-    nblk = _T().ln_backward_split(dy, x, g.master, mean, rstd, dx, ws, addend)
+    nblk = _T().ln_backward_split(dy, x, g.master, mean, rstd, dx, ws, addend, *extra)
     _DEFER_LNRED.append((ws, nblk, g, b))
     return True
 
@@ -889,10 +1022,16 @@ class _AddLNSkip(Function):
     """(s, LN(s)) with s = x + r: the residual add of a pre-LN block fused
     into the next LayerNorm's forward (one kernel writes s and LN(s)); the
     backward is _LNSkip's (dskip summed in the LN backward kernel) and hands
-    ds to both addends."""
+    ds to both addends.
+
+    drop = (record, site, thr, scale): training dropout on r inside the same
+    kernels, s = x + dropout(r). The forward kernel draws the mask while it
+    reads r; the backward kernel regenerates it and writes the second output
+    dr = keep ? ds * scale : 0 from the ds it holds in registers, so the
+    backward returns (ds, dr) with no extra pass and no stored mask."""
 
     @staticmethod
-    def forward(ctx, x, r, token, g: Param, b: Param, eps: float):
+    def forward(ctx, x, r, token, g: Param, b: Param, eps: float, drop=None):
         ctx.set_materialize_grads(False)         # see _LNSkip.forward
         D = x.shape[-1]
         rows = x.numel() // D
@@ -901,30 +1040,60 @@ class _AddLNSkip(Function):
             y = torch.empty_like(x)
             mean = torch.empty(rows, dtype=torch.float32, device=x.device)
             rstd = torch.empty_like(mean)
-            _T().ln_forward(x, g.master, b.master, y, mean, rstd, eps, r, sm)
+            if drop is None:
+                _T().ln_forward(x, g.master, b.master, y, mean, rstd, eps, r, sm)
+            else:
+                _T().ln_forward(x, g.master, b.master, y, mean, rstd, eps, r, sm, *drop)
         else:
-            sm = (x.float() + r.float()).to(BF16)
+            if drop is None:
+                sm = (x.float() + r.float()).to(BF16)
+            else:
+                # the kernel's rounding: fp32 product, fp32 sum, one bf16 rounding;
+                # a dropped position keeps x's bits
+                sc = torch.tensor(drop[3], dtype=torch.float32)
+                sm = torch.where(_cpu_keep(x, drop), (x.float() + r.float() * sc).to(BF16), x)
             sf = sm.float().reshape(rows, D)
             mean = sf.mean(1)
             rstd = torch.rsqrt(sf.var(1, unbiased=False) + eps)
             y = (((sf - mean[:, None]) * rstd[:, None]) * g.master + b.master).reshape(x.shape).to(BF16)
-        ctx.g, ctx.b = g, b
+        ctx.g, ctx.b, ctx.drop = g, b, drop
         ctx.save_for_backward(sm, mean, rstd)
         return sm, y
 
     @staticmethod
     def backward(ctx, dskip, dy):
+        drop = ctx.drop
+        if drop is None:
+            ds = _LNSkip.backward(ctx, dskip, dy)[0]
+            return ds, ds, None, None, None, None, None
+        if dy is None:                           # only the skip output was used
+            if dskip is None:
+                return None, None, None, None, None, None, None
+            return dskip, _dropout_apply(dskip.contiguous(), drop), None, None, None, None, None
+        if dy.is_cuda:
+            x, mean, rstd = ctx.saved_tensors
+            g, b = ctx.g, ctx.b
+            ds = torch.empty_like(x)
+            dr = torch.empty_like(x)
+            if not _ln_backward(dy.contiguous(), x, g, b, mean, rstd, ds,
+                                dskip.contiguous() if dskip is not None else None, dr, drop):
+                g.grad_ready()
+                b.grad_ready()
+            return ds, dr, None, None, None, None, None
         ds = _LNSkip.backward(ctx, dskip, dy)[0]
-        return ds, ds, None, None, None, None
+        return ds, _dropout_apply(ds, drop), None, None, None, None, None
 
 
-def add_layernorm_skip(x: torch.Tensor, r: torch.Tensor, g: Param, b: Param, eps: float = 1e-5):
-    """(x + r, layernorm(x + r)) in one kernel: ``layernorm_skip(add(x, r))``."""
+def add_layernorm_skip(x: torch.Tensor, r: torch.Tensor, g: Param, b: Param, eps: float = 1e-5,
+                       drop: Optional[float] = None):
+    """(x + r, layernorm(x + r)) in one kernel: ``layernorm_skip(add(x, r))``.
+    drop: dropout probability applied to r inside the kernel (a site of the
+    installed record, see ``dropout``): ``layernorm_skip(add(x, dropout(r, drop)))``."""
     if not x.is_contiguous():
         x = x.contiguous()
     if not r.is_contiguous():
         r = r.contiguous()
-    return _AddLNSkip.apply(x, r, g.arena.token, g, b, eps)
+    return _AddLNSkip.apply(x, r, g.arena.token, g, b, eps, _drop_args(drop))
 
 
 # ============================================================ pooling

@@ -786,6 +786,23 @@ def comm_size(group) -> int:
     return dist.get_world_size(group)
 
 
+def comm_rank(group) -> int:
+    """This process's position within a gang comm or a plain process group
+    (0 without one): distinct per member, the same on every resume over the
+    same rank set."""
+    if group is None:
+        return 0
+    ranks = getattr(group, "ranks", None)
+    if ranks and dist.is_available() and dist.is_initialized() and dist.get_rank() in ranks:
+        return tuple(ranks).index(dist.get_rank())
+    r = getattr(group, "rank", None)
+    if isinstance(r, int):
+        return r
+    if ranks is not None:
+        return 0
+    return dist.get_rank(group)
+
+
 class _PlainPG:
     """A torch.distributed process group behind the GangPG interface."""
 
