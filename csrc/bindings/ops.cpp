@@ -1242,22 +1242,44 @@ void check_attn_view(const Tensor& t, const char* name) {
   // tensor viewed transposed), 16-byte aligned rows
   TORCH_CHECK(t.stride(1) % 8 == 0 && t.stride(0) % 8 == 0, "tam.attn: ", name, " stride alignment");
 }
+// the attention-dropout arguments: as drop_args, with thr = round(p * 256) in
+// (0, 256), scale = 256 / (256 - thr), and the mask contract's size limits
+// (tam/philox.h: block indices in 16 bits, the head index in 32)
+static tam::LnDrop attn_drop_args(const optional<Tensor>& rec, int64_t site, int64_t thr, double scale,
+                                  const Tensor& q, const Tensor& k, const char* op) {
+  tam::LnDrop d;
+  if (!(rec.has_value() && rec->defined())) return d;
+  TORCH_CHECK(rec->scalar_type() == at::kInt && rec->numel() >= 4 && rec->is_contiguous() &&
+                  rec->device() == q.device(),
+              op, ": drop_rec must be an int32 [4] tensor on the data's device");
+  TORCH_CHECK(thr > 0 && thr < 256 && site >= 0 && site <= 0x7fffffff, op, ": drop_thr in (0, 256), drop_site >= 0");
+  TORCH_CHECK(q.size(1) <= 262144 && k.size(1) <= 262144 && q.size(0) * q.size(2) <= (int64_t)1 << 32, op,
+              ": attention dropout needs Sq, Sk <= 262144 and B*H <= 2^32");
+  d.rec = rec->data_ptr<int>();
+  d.site = (unsigned)site;
+  d.thr = (unsigned)thr;
+  d.scale = (float)scale;
+  return d;
+}
 void attn_forward_op(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
-                     const Tensor& lse, bool causal, double scale, const optional<Tensor>& kv_len) {
+                     const Tensor& lse, bool causal, double scale, const optional<Tensor>& kv_len,
+                     const optional<Tensor>& drop_rec, int64_t drop_site, int64_t drop_thr, double drop_scale) {
   check_attn_view(q, "q"); check_attn_view(k, "k"); check_attn_view(v, "v"); check_attn_view(o, "o");
   TORCH_CHECK(k.stride(1) == v.stride(1), "tam.attn: k/v token strides differ");
   check_f32(lse, "lse");
   const int B = (int)q.size(0), Sq = (int)q.size(1), H = (int)q.size(2), Sk = (int)k.size(1);
   TORCH_CHECK(lse.numel() == (int64_t)B * H * Sq, "tam.attn: lse size");
   TORCH_CHECK(k.stride(0) == v.stride(0), "tam.attn: k/v batch strides differ");
+  const tam::LnDrop drop = attn_drop_args(drop_rec, drop_site, drop_thr, drop_scale, q, k, "tam.attn_forward");
   tam::attn_forward(bp(q), bp(k), bp(v), bpm(o), lse.data_ptr<float>(), B, H, Sq, Sk, q.stride(1),
                     k.stride(1), o.stride(1), q.stride(0), k.stride(0), o.stride(0), causal, (float)scale,
-                    opt_ptr<const int>(kv_len), cur_stream(q));
+                    opt_ptr<const int>(kv_len), cur_stream(q), drop);
 }
 void attn_backward_op(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                       const Tensor& dout, const Tensor& lse, const Tensor& dq, const Tensor& dk,
                       const Tensor& dv, const Tensor& dq_acc, const Tensor& delta, bool causal,
-                      double scale, const optional<Tensor>& kv_len) {
+                      double scale, const optional<Tensor>& kv_len, const optional<Tensor>& drop_rec,
+                      int64_t drop_site, int64_t drop_thr, double drop_scale) {
   check_attn_view(q, "q"); check_attn_view(k, "k"); check_attn_view(v, "v"); check_attn_view(o, "o");
   check_attn_view(dout, "dout"); check_attn_view(dq, "dq"); check_attn_view(dk, "dk");
   check_attn_view(dv, "dv");
@@ -1270,11 +1292,12 @@ void attn_backward_op(const Tensor& q, const Tensor& k, const Tensor& v, const T
   check_f32(dq_acc, "dq_acc"); check_f32(delta, "delta");
   TORCH_CHECK(dq_acc.numel() >= (int64_t)B * Sq * H * 64 && delta.numel() >= (int64_t)B * H * Sq,
               "tam.attn_bwd: workspace sizes");
+  const tam::LnDrop drop = attn_drop_args(drop_rec, drop_site, drop_thr, drop_scale, q, k, "tam.attn_backward");
   tam::attn_backward(bp(q), bp(k), bp(v), bp(o), bp(dout), lse.data_ptr<float>(), bpm(dq), bpm(dk),
                      bpm(dv), dq_acc.data_ptr<float>(), delta.data_ptr<float>(), B, H, Sq, Sk,
                      q.stride(1), k.stride(1), o.stride(1), q.stride(0), k.stride(0), o.stride(0), causal,
                      (float)scale,
-                     opt_ptr<const int>(kv_len), cur_stream(q));
+                     opt_ptr<const int>(kv_len), cur_stream(q), drop);
 }
 
 // ------------------------------------------------------------------ LSTM
@@ -1467,8 +1490,8 @@ TORCH_LIBRARY(tam, m) {
   m.def("grad_clip_finalize(Tensor partials, float max_norm, float gscale, Tensor(a!) clip) -> ()", &grad_clip_finalize_op);
   m.def("grad_sumsq_blocks(int n) -> int", &grad_sumsq_blocks_op);
   m.def("lstm_guard_step(Tensor(a!) err) -> ()", &lstm_guard_step_op);
-  m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len) -> ()", &attn_forward_op);
-  m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len) -> ()", &attn_backward_op);
+  m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_forward_op);
+  m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_backward_op);
   m.def("lstm_step_forward(Tensor gx, Tensor w_hh, Tensor? h_prev, Tensor? c_prev, Tensor(a!) c_out, Tensor(b!) h_out, Tensor(c!) act) -> ()", &lstm_step_fwd_op);
   m.def("lstm_seq_forward(Tensor gx, Tensor w_hh, Tensor(a!) hs, Tensor(b!) cs, Tensor(c!) act, bool reverse, Tensor(d!) sync, Tensor(e!)? job_err=None, int grids=-1, int reserved_cus=0, bool zeroed=False) -> bool", &lstm_seq_fwd_op);
   m.def("lstm_seq_backward(Tensor act, Tensor cs, Tensor dH, Tensor w_hh, Tensor(a!) dG, bool reverse, Tensor(b!) sync, Tensor(c!)? job_err=None, int grids=-1, int reserved_cus=0, bool zeroed=False) -> bool", &lstm_seq_bwd_op);

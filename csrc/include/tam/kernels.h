@@ -62,8 +62,8 @@ void bn_backward(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const 
 struct LnDrop {
   const int* rec = nullptr;   // the trainer's dropout record, int32[4] {seed, stream, step, 0}
   unsigned site = 0;          // ordinal of the dropout call within the forward
-  unsigned thr = 0;           // round(p * 65536): kept iff u16 >= thr
-  float scale = 1.f;          // 65536 / (65536 - thr)
+  unsigned thr = 0;           // round(p * 65536): kept iff u16 >= thr (attention: p * 256, u8)
+  float scale = 1.f;          // 65536 / (65536 - thr) (attention: 256 / (256 - thr))
 };
 void ln_forward(const bf16_t* x, const float* g, const float* b, bf16_t* y, float* mean,
                 float* rstd, long rows, int D, float eps, hipStream_t s, const bf16_t* addend = nullptr,
@@ -159,15 +159,20 @@ void grad_clip_finalize(const double* partials, int slots, float max_norm, float
 // fused attention (bf16, head_dim 64): element (b, s, h, d) at b * *_bstride +
 // s * *_stride + 64 h + d (batch-major [B][S][H][64], or a time-major
 // [S][B][H][64] tensor with bstride = H*64 per batch row)
+// drop (rec != nullptr): attention-probability dropout, O = (keep * P) V * scale
+// with the LSE of the undropped scores; site is the attention call's ordinal,
+// thr = round(p * 256) in (0, 256), scale = 256 / (256 - thr); mask contract
+// in tam/philox.h. The backward regenerates the mask from the same arguments.
 void attn_forward(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, int B,
                   int H, int Sq, int Sk, long q_stride, long kv_stride, long o_stride, long q_bstride,
-                  long kv_bstride, long o_bstride, int causal, float scale, const int* kv_len, hipStream_t s);
+                  long kv_bstride, long o_bstride, int causal, float scale, const int* kv_len, hipStream_t s,
+                  LnDrop drop = {});
 void attn_short_policy(int p);   // 1: Sk <= 128 backward in one fused launch (default)
 void attn_backward(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o,
                    const bf16_t* dout, const float* lse, bf16_t* dq, bf16_t* dk, bf16_t* dv,
                    float* dq_acc, float* delta, int B, int H, int Sq, int Sk, long q_stride,
                    long kv_stride, long o_stride, long q_bstride, long kv_bstride, long o_bstride, int causal,
-                   float scale, const int* kv_len, hipStream_t s);
+                   float scale, const int* kv_len, hipStream_t s, LnDrop drop = {});
 
 // LSTM cell pointwise (gates = x W_ih^T + h W_hh^T + b precomputed, fp32)
 void lstm_cell_forward(const float* gates, const float* c_prev, float* c_out, bf16_t* h_out,

@@ -10,6 +10,25 @@
 // thr = round(p * 65536) in (0, 65536). Kept elements are scaled by
 // fp32(65536) / fp32(65536 - thr), dropped ones become +0. Nothing is stored:
 // the backward regenerates the mask from the same (record, site).
+//
+// Attention-probability mask contract (README "Training dropout"; tests
+// rebuild it on the host): a pure function of the logical position
+// (b, h, q, kv) in the [B,H,Sq,Sk] probability tensor, (b, q) indexing the
+// [B,S,H,64] views the attention kernels take. One Philox call covers a block
+// of 4 queries x 4 keys, block (Q, K) = (q >> 2, kv >> 2):
+//   counter = (K | (Q << 16), b*H + h, 0x80000000 | a, step), key = (seed, stream),
+//   u = (out[q & 3] >> (8 * (kv & 3))) & 0xff, kept iff u >= thr,
+// thr = round(p * 256) in (0, 256), so p is quantised to 1/256. a is the
+// attention call's ordinal within the forward, from a counter of its own: the
+// elementwise sites above keep their ordinals whether or not attention dropout
+// is on, and the top bit of the site word keeps the two spaces apart. Kept
+// probabilities are scaled by fp32(256) / fp32(256 - thr). Sq, Sk <= 262144
+// (Q, K fit 16 bits) and B*H <= 2^32.
+// Why 4 x 4: the forward kernel's lane holds 4 consecutive keys of one query
+// (one output word), both backward kernels' lane holds 4 consecutive queries
+// of one key (one byte of each of the four words), so either direction eats
+// whole Philox outputs. The running max, row sum and LSE come from the
+// undropped scores: O = (keep * P) V * scale, LSE unchanged.
 #pragma once
 #include <stdint.h>
 
@@ -62,6 +81,15 @@ TAM_HD uint32_t drop_keep8(uint64_t q, uint32_t site, const DropRec& r, uint32_t
     bits |= ((o[i] >> 16) >= thr ? 1u : 0u) << (2 * i + 1);
   }
   return bits;
+}
+
+// the four words of attention-mask block (Q, K) = (q >> 2, kv >> 2) of head
+// bh = b*H + h at attention call ordinal a: word q & 3, byte kv & 3
+TAM_HD void attn_drop_block(uint32_t Q, uint32_t K, uint32_t bh, uint32_t a, const DropRec& r,
+                            uint32_t (&out)[4]) {
+  const uint32_t ctr[4] = {K | (Q << 16), bh, 0x80000000u | a, r.step};
+  const uint32_t key[2] = {r.seed, r.stream};
+  philox4x32_10(ctr, key, out);
 }
 
 }  // namespace tam

@@ -15,9 +15,18 @@
 // and keeps dK^T / dV^T in registers across the whole query sweep; S and dP
 // are recomputed per 64-query tile (P = exp(S*scale - LSE)), dS crosses LDS
 // once (for dQ), dQ is summed across key blocks with fp32 atomics.
+//
+// DROP (all three kernels): attention-probability dropout, mask contract in
+// tam/philox.h. One Philox call covers 4 queries x 4 keys; the four lanes of a
+// quad (lane & ~3) always hold the same four blocks of a 64 x 64 tile, so lane
+// i computes block i only and the quad trades words by DPP quad broadcasts
+// (16 v_mov_dpp per tile against three more 10-round Philox calls, ~100 VALU
+// ops each with quarter-rate 32-bit multiplies). The mask is regenerated in the
+// backward, nothing is stored. DROP = false is the kernel as it was.
 #include "tam/common.h"
 #include "tam/igemm.h"
 #include "tam/kernels.h"
+#include "tam/philox.h"
 
 namespace tam {
 
@@ -78,7 +87,56 @@ __device__ __forceinline__ f32x4_t mfma(const s16x8_t& a, const s16x8_t& b, cons
                                                  __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
 
+// every lane of a quad (4 consecutive lanes) reads quad lane T's value
+template <int T>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, T * 0x55, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t sel4(int i, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  return i == 0 ? a : i == 1 ? b : i == 2 ? c : d;
+}
+__device__ __forceinline__ uint32_t keep4(uint32_t word, uint32_t thr) {
+  uint32_t k = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) k |= (((word >> (8 * r)) & 0xffu) >= thr ? 1u : 0u) << r;
+  return k;
+}
+// Forward keep bits of one 64-key tile: bit 4t + r = key kb + 16t + r (kb =
+// k0 + 4g) of query qw is kept. Quad lane i draws block (qw >> 2, (kb + 16i) >> 2);
+// lane j then needs word j = qw & 3 of every block.
+__device__ __forceinline__ uint32_t attn_keep_fwd(int qw, int kb, uint32_t bh, const LnDrop& drop,
+                                                  const DropRec& dr, int lane) {
+  const int i = lane & 3;
+  uint32_t o[4];
+  attn_drop_block((uint32_t)qw >> 2, (uint32_t)(kb + 16 * i) >> 2, bh, drop.site, dr, o);
+  uint32_t keep = 0;
+#define TAM_FWD_WORD(T)                                                                          \
+  keep |= keep4(sel4(i, quad_bcast<T>(o[0]), quad_bcast<T>(o[1]), quad_bcast<T>(o[2]),           \
+                     quad_bcast<T>(o[3])), drop.thr) << (4 * T)
+  TAM_FWD_WORD(0); TAM_FWD_WORD(1); TAM_FWD_WORD(2); TAM_FWD_WORD(3);
+#undef TAM_FWD_WORD
+  return keep;
+}
+// Backward keep bits of one 64-query tile: bit 4t + r = query qb + 16t + r (qb
+// = q0 + 4g) of key kvw is kept. Quad lane i draws block ((qb + 16i) >> 2,
+// kvw >> 2); lane j needs byte j = kvw & 3 of all four words of every block.
+__device__ __forceinline__ uint32_t attn_keep_bwd(int qb, int kvw, uint32_t bh, const LnDrop& drop,
+                                                  const DropRec& dr, int lane) {
+  const int i = lane & 3;
+  uint32_t o[4];
+  attn_drop_block((uint32_t)(qb + 16 * i) >> 2, (uint32_t)kvw >> 2, bh, drop.site, dr, o);
+  uint32_t keep = 0;
+#define TAM_BWD_BYTE(T, R) \
+  keep |= (((quad_bcast<T>(o[R]) >> (8 * i)) & 0xffu) >= drop.thr ? 1u : 0u) << (4 * T + R)
+#define TAM_BWD_BLOCK(T) TAM_BWD_BYTE(T, 0); TAM_BWD_BYTE(T, 1); TAM_BWD_BYTE(T, 2); TAM_BWD_BYTE(T, 3)
+  TAM_BWD_BLOCK(0); TAM_BWD_BLOCK(1); TAM_BWD_BLOCK(2); TAM_BWD_BLOCK(3);
+#undef TAM_BWD_BLOCK
+#undef TAM_BWD_BYTE
+  return keep;
+}
+
 // ============================================================== forward
+template <bool DROP>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict__ Q,
                                                         const bf16_t* __restrict__ K,
                                                         const bf16_t* __restrict__ V,
@@ -87,7 +145,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
                                                         int Sk, long qs, long kvs, long os,
                                                         long qb, long kvb, long ob,
                                                         int causal, float scale,
-                                                        const int* __restrict__ kv_len) {
+                                                        const int* __restrict__ kv_len, LnDrop drop) {
   __shared__ __attribute__((aligned(16))) char smem[2 * AT * AD * 2];
   char* kt = smem;
   char* vt = smem + AT * AD * 2;
@@ -96,6 +154,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
   const int q0 = blockIdx.x * AT;
   const int qw = q0 + 16 * w + (lane & 15);   // this lane's query
   const int klen = kv_len ? min(Sk, kv_len[b]) : Sk;
+  DropRec dr{};
+  if (DROP) dr = DropRec{(uint32_t)drop.rec[0], (uint32_t)drop.rec[1], (uint32_t)drop.rec[2]};
 
   const bf16_t* Qb = Q + (long)b * qb + h * AD;
   const bf16_t* Kb = K + (long)b * kvb + h * AD;
@@ -170,6 +230,15 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
     m = mn;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) o[mt] *= alpha;
+    if (DROP) {
+      // after the row sum: m, l and the LSE are those of the undropped scores
+      const uint32_t keep = attn_keep_fwd(qw, k0 + 4 * g, (uint32_t)bh, drop, dr, lane);
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (!((keep >> (4 * t + r)) & 1u)) st[t][r] = 0.f;
+    }
     // O^T[d][q] += V^T[d][kv] P^T[kv][q]
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -180,7 +249,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
     }
   }
   if (qw < Sq) {
-    const float inv = l > 0.f ? 1.f / l : 0.f;
+    float inv = l > 0.f ? 1.f / l : 0.f;
+    if (DROP) inv *= drop.scale;
     bf16_t* Ob = O + (long)b * ob + (long)qw * os + h * AD;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
@@ -212,12 +282,13 @@ __global__ void attn_delta_kernel(const bf16_t* __restrict__ O, const bf16_t* __
 }
 
 // ============================================================== backward
+template <bool DROP>
 __global__ void __launch_bounds__(256) attn_bwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ DELTA,
     bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, float* __restrict__ dQacc, int H, int Sq,
     int Sk, long qs, long kvs, long os, long qb, long kvb, long ob, int causal, float scale,
-    const int* __restrict__ kv_len) {
+    const int* __restrict__ kv_len, LnDrop drop) {
   // LDS: Q row image, Q^T image (rho), dO row image, dO^T image (rho), K^T image, dS image,
   //      lse[64], delta[64]
   __shared__ __attribute__((aligned(16))) char smem[6 * AT * AD * 2 + 2 * AT * 4];
@@ -260,6 +331,8 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) dvt[mt] = dkt[mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const float sl2 = scale * kLog2e;
+  DropRec dr{};
+  if (DROP) dr = DropRec{(uint32_t)drop.rec[0], (uint32_t)drop.rec[1], (uint32_t)drop.rec[2]};
 
   const int qstart = causal ? (k0 / AT) * AT : 0;
   for (int q0 = qstart; q0 < Sq; q0 += AT) {
@@ -289,6 +362,9 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
       }
     }
     // P = exp2(S*scale*log2e - lse*log2e); dS = P * (dP - delta)
+    // DROP: dV takes keep * P (its scale at the final store), dP = keep * dP * scale
+    uint32_t keep = 0;
+    if (DROP) keep = attn_keep_bwd(q0 + 4 * g, kvw, (uint32_t)bh, drop, dr, lane);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -297,8 +373,14 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
         const int q = q0 + ql;
         float p = exp2f(sp[t][r] * sl2 - s_lse[ql]);
         if (q >= Sq || kvw >= klen || (causal && kvw > q)) p = 0.f;
-        sp[t][r] = p;
-        dp[t][r] = p * (dp[t][r] - s_del[ql]);
+        if (DROP) {
+          const bool kp = (keep >> (4 * t + r)) & 1u;
+          sp[t][r] = kp ? p : 0.f;
+          dp[t][r] = p * ((kp ? dp[t][r] * drop.scale : 0.f) - s_del[ql]);
+        } else {
+          sp[t][r] = p;
+          dp[t][r] = p * (dp[t][r] - s_del[ql]);
+        }
       }
     // dV^T[d][kv] += dO^T[d][q] P[q][kv] ; dK^T[d][kv] += Q^T[d][q] dS[q][kv]
 #pragma unroll
@@ -344,6 +426,10 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
   if (kvw < Sk) {
     bf16_t* dKb = dK + (long)b * kvb + (long)kvw * kvs + h * AD;
     bf16_t* dVb = dV + (long)b * kvb + (long)kvw * kvs + h * AD;
+    if (DROP) {
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) dvt[mt] *= drop.scale;
+    }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
       const int d = 16 * mt + 4 * g;
@@ -364,12 +450,13 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
 // dO and O tile images. One launch instead of delta+zero / backward /
 // fp32-dQ cast, and no dQ atomics.
 constexpr int ATS_K = 128;
+template <bool DROP>
 __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, const float* __restrict__ LSE,
     bf16_t* __restrict__ dQ, bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, int H, int Sq, int Sk,
     long qs, long kvs, long os, long qb, long kvb, long ob, int causal, float scale,
-    const int* __restrict__ kv_len) {
+    const int* __restrict__ kv_len, LnDrop drop) {
   // LDS: Q row image, Q^T image (rho), dO row image, dO^T image (rho), O row
   //      image (delta), K [kv][d] image (128 rows), dS [kv][q] image (128 rows),
   //      lse[64], delta[64]
@@ -433,6 +520,8 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) dvt[mt] = dkt[mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const float sl2 = scale * kLog2e;
+  DropRec dr{};
+  if (DROP) dr = DropRec{(uint32_t)drop.rec[0], (uint32_t)drop.rec[1], (uint32_t)drop.rec[2]};
 
   for (int q0 = 0; q0 < Sq; q0 += AT) {
     // half 0 stages Q, half 1 stages dO and O (fetched one tile ahead)
@@ -476,6 +565,8 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
         dp[t] = mfma(read_frag_k(do_k, lane, 16 * t, ks), vf[ks], dp[t]);
       }
     }
+    uint32_t keep = 0;
+    if (DROP) keep = attn_keep_bwd(q0 + 4 * g, kvw, (uint32_t)bh, drop, dr, lane);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -484,8 +575,14 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
         const int q = q0 + ql;
         float p = exp2f(sp[t][r] * sl2 - s_lse[ql]);
         if (q >= Sq || kvw >= klen || (causal && kvw > q)) p = 0.f;
-        sp[t][r] = p;
-        dp[t][r] = p * (dp[t][r] - s_del[ql]);
+        if (DROP) {
+          const bool kp = (keep >> (4 * t + r)) & 1u;
+          sp[t][r] = kp ? p : 0.f;
+          dp[t][r] = p * ((kp ? dp[t][r] * drop.scale : 0.f) - s_del[ql]);
+        } else {
+          sp[t][r] = p;
+          dp[t][r] = p * (dp[t][r] - s_del[ql]);
+        }
       }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -529,6 +626,10 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
   if (kvw < Sk) {
     bf16_t* dKb = dK + (long)b * kvb + (long)kvw * kvs + h * AD;
     bf16_t* dVb = dV + (long)b * kvb + (long)kvw * kvs + h * AD;
+    if (DROP) {
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) dvt[mt] *= drop.scale;
+    }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
       const int d = 16 * mt + 4 * g;
@@ -551,10 +652,15 @@ __global__ void attn_dq_cast_kernel(const float* __restrict__ acc, bf16_t* __res
 
 void attn_forward(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, int B,
                   int H, int Sq, int Sk, long q_stride, long kv_stride, long o_stride, long q_bstride,
-                  long kv_bstride, long o_bstride, int causal, float scale, const int* kv_len, hipStream_t s) {
+                  long kv_bstride, long o_bstride, int causal, float scale, const int* kv_len, hipStream_t s,
+                  LnDrop drop) {
   dim3 grid((Sq + AT - 1) / AT, B * H);
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(256), 0, s, q, k, v, o, lse, H, Sq, Sk, q_stride,
-                     kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal, scale, kv_len);
+#define TAM_ATTN_FWD(DR)                                                                                  \
+  hipLaunchKernelGGL(attn_fwd_kernel<DR>, grid, dim3(256), 0, s, q, k, v, o, lse, H, Sq, Sk, q_stride,   \
+                     kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal, scale, kv_len, drop)
+  if (drop.rec) TAM_ATTN_FWD(true);
+  else TAM_ATTN_FWD(false);
+#undef TAM_ATTN_FWD
 }
 
 // 1 (default): key ranges <= 128 take the one-launch short-sequence backward;
@@ -567,11 +673,15 @@ void attn_backward(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16
                    const bf16_t* dout, const float* lse, bf16_t* dq, bf16_t* dk, bf16_t* dv,
                    float* dq_acc, float* delta, int B, int H, int Sq, int Sk, long q_stride,
                    long kv_stride, long o_stride, long q_bstride, long kv_bstride, long o_bstride, int causal,
-                   float scale, const int* kv_len, hipStream_t s) {
+                   float scale, const int* kv_len, hipStream_t s, LnDrop drop) {
   if (Sk <= ATS_K && g_attn_short) {
-    hipLaunchKernelGGL(attn_bwd_short_kernel, dim3(B * H), dim3(512), 0, s, q, k, v, o, dout, lse, dq, dk, dv,
-                       H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal, scale,
-                       kv_len);
+#define TAM_ATTN_BWD_SHORT(DR)                                                                                 \
+  hipLaunchKernelGGL(attn_bwd_short_kernel<DR>, dim3(B * H), dim3(512), 0, s, q, k, v, o, dout, lse, dq, dk,  \
+                     dv, H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal,  \
+                     scale, kv_len, drop)
+    if (drop.rec) TAM_ATTN_BWD_SHORT(true);
+    else TAM_ATTN_BWD_SHORT(false);
+#undef TAM_ATTN_BWD_SHORT
     return;
   }
   const long rows = (long)B * H * Sq;
@@ -579,9 +689,13 @@ void attn_backward(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16
                      B, H, Sq, o_stride, o_bstride);
   const long nq = (long)B * Sq * H * AD;
   dim3 grid((Sk + AT - 1) / AT, B * H);
-  hipLaunchKernelGGL(attn_bwd_kernel, grid, dim3(256), 0, s, q, k, v, dout, lse, delta, dk, dv,
-                     dq_acc, H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal,
-                     scale, kv_len);
+#define TAM_ATTN_BWD(DR)                                                                                  \
+  hipLaunchKernelGGL(attn_bwd_kernel<DR>, grid, dim3(256), 0, s, q, k, v, dout, lse, delta, dk, dv, dq_acc, \
+                     H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal,  \
+                     scale, kv_len, drop)
+  if (drop.rec) TAM_ATTN_BWD(true);
+  else TAM_ATTN_BWD(false);
+#undef TAM_ATTN_BWD
   long blocks = (nq + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(attn_dq_cast_kernel, dim3(blocks), dim3(256), 0, s, dq_acc, dq, nq, H * AD, Sq,

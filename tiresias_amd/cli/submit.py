@@ -7,7 +7,7 @@ Examples::
 
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --gpus 2 --iterations 800
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model gnmt --duration 30 --grad-clip 5.0
-    python -m tiresias_amd.cli.submit --spool /tmp/tam --model transformer --iterations 800 --dropout 0.1
+    python -m tiresias_amd.cli.submit --spool /tmp/tam --model transformer --iterations 800 --dropout 0.1 --attn-dropout 0.1
     python -m tiresias_amd.cli.submit --spool /tmp/tam --status
     python -m tiresias_amd.cli.submit --spool /tmp/tam --shutdown
 """
@@ -33,6 +33,10 @@ def main(argv=None) -> int:
                     help="clip the gradient's global L2 norm to this value; non-finite steps are skipped")
     ap.add_argument("--dropout", type=float,
                     help="training dropout probability at the model's dropout sites (0 <= p < 1)")
+    ap.add_argument("--attn-dropout", type=float,
+                    help="dropout probability on the attention probabilities, inside the attention kernels "
+                         "(0 <= p < 1, quantised to 1/256: 0.1 drops 26/256); models without attention "
+                         "dropout ignore it")
     ap.add_argument("--status", action="store_true")
     ap.add_argument("--shutdown", action="store_true", help="stop serving once the cluster drains")
     a = ap.parse_args(argv)
@@ -47,7 +51,8 @@ def main(argv=None) -> int:
     if not a.model or (a.iterations is None and a.duration is None):
         ap.error("--model and one of --iterations / --duration are required")
     jid = sp.submit(a.model, a.gpus, iterations=a.iterations, duration=a.duration, job_id=a.job_id,
-                    batch=a.batch, grad_clip=a.grad_clip, dropout=a.dropout)
+                    batch=a.batch, grad_clip=a.grad_clip, dropout=a.dropout,
+                    attn_dropout=a.attn_dropout)
     print(jid)
     return 0
 

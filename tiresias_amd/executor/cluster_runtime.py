@@ -148,6 +148,7 @@ class ReplayJob:
     batch: Optional[int] = None
     grad_clip: Optional[float] = None    # global-norm gradient clip of the job (None = off)
     dropout: Optional[float] = None      # training dropout of the job (None = off)
+    attn_dropout: Optional[float] = None     # attention-probability dropout of the job (None = off)
 
 
 class Controller:
@@ -509,7 +510,7 @@ class Controller:
         now = self.now()
         for req in self.spool.poll():
             try:
-                jid, model, g, iters, batch, clip, drop = self._validate(req)
+                jid, model, g, iters, batch, clip, drop, adrop = self._validate(req)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -522,7 +523,7 @@ class Controller:
             spec = JobSpec(job_id=jid, submit_time=now, duration=iters * self._iter_est(model, g),
                            num_gpu=g, model=model, iterations=iters)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
-                                        dropout=drop)
+                                        dropout=drop, attn_dropout=adrop)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -531,7 +532,7 @@ class Controller:
 
     def _validate(self, req: dict):
         """Untrusted spool request -> (job_id, model, num_gpu, iterations,
-        batch, grad_clip, dropout); raises ValueError with the rejection
+        batch, grad_clip, dropout, attn_dropout); raises ValueError with the rejection
         reason."""
         from ..models import MODELS
 
@@ -578,7 +579,13 @@ class Controller:
                     or round(drop * 65536) >= 65536):
                 raise ValueError(f"dropout must be a number p with 0 <= p < 1 (quantised to 1/65536), got {drop!r}")
             drop = float(drop)
-        return jid, model, g, iters, batch, clip, drop
+        adrop = req.get("attn_dropout")
+        if adrop is not None:
+            if (isinstance(adrop, bool) or not isinstance(adrop, (int, float)) or not 0 <= adrop < 1
+                    or round(adrop * 256) >= 256):
+                raise ValueError(f"attn_dropout must be a number p with 0 <= p < 1 (quantised to 1/256), got {adrop!r}")
+            adrop = float(adrop)
+        return jid, model, g, iters, batch, clip, drop, adrop
 
     def status(self) -> dict:
         s = self.sched
@@ -640,6 +647,7 @@ class Controller:
                 act = {"op": "start", "job": j.job_id, "ranks": ranks, "model": rj.model,
                        "iters": max(0, rj.iterations - self.done_iters[j.job_id]),
                        "batch": rj.batch, "grad_clip": rj.grad_clip, "dropout": rj.dropout,
+                       "attn_dropout": rj.attn_dropout,
                        "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
@@ -894,13 +902,15 @@ class Worker:
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
             t.set_dropout(act.get("dropout"))        # likewise (a change re-captures the graph)
+            t.set_attn_dropout(act.get("attn_dropout"))
             self._bind(t, ranks)
             if want and not t.use_graph and t.ddp is None:
                 t.enable_graph()
             return t
         t = Trainer(act["model"], self.device, batch=act.get("batch"), group=self._group(ranks),
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
-                    ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"))
+                    ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
+                    attn_dropout=act.get("attn_dropout"))
         t.pool_key = key
         return t
 

@@ -28,11 +28,13 @@ class Trainer:
                  model_kwargs: Optional[dict] = None, lr: Optional[float] = None,
                  overlap_wgrad: Optional[bool] = None, branches: Optional[bool] = None,
                  ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
-                 dropout: Optional[float] = None):
+                 dropout: Optional[float] = None, attn_dropout: Optional[float] = None):
         self.model_name = model
         self.spec = MODELS[model]
         if dropout is None:
             dropout = self.spec.dropout
+        if attn_dropout is None:
+            attn_dropout = self.spec.attn_dropout
         if grad_clip is None:
             grad_clip = self.spec.clip
         if grad_clip is not None and ddp_shard and group is not None and comm_size(group) > 1:
@@ -93,12 +95,15 @@ class Trainer:
         self._clip_part = None          # grad_sumsq's per-block fp64 partials
         self._clip_host = [1.0, 0.0, 0, 0]   # the same four words on the CPU path
         self.set_grad_clip(grad_clip)
-        # training dropout (set_dropout); None = off, nothing allocated or
-        # launched
+        # training dropout (set_dropout) and attention-probability dropout
+        # (set_attn_dropout); None = off, and with both off nothing is
+        # allocated or launched. They share the record and its one advance
         self.dropout: Optional[float] = None
+        self.attn_dropout: Optional[float] = None
         self._drop_rec = None           # int32[4] {seed, stream, step, 0} on the trainer's device
         self._drop_at = None            # (seed, stream, step) the record holds, tracked on the host
         self.set_dropout(dropout)
+        self.set_attn_dropout(attn_dropout)
         # weight init and the synthetic batch were queued on the stream that
         # built the trainer; a step issued from another stream (GPU sharing
         # runs each job on its own stream) must wait for them first
@@ -132,7 +137,7 @@ class Trainer:
             # (an early flush on a side stream measured slower: ResNet-50 9.07
             # vs 8.89 ms, Transformer 5.41 vs 5.30; removed in round 6)
             Fx.defer_wgrad(True)
-        drop = self._drop_rec if self.dropout else None
+        drop = self._drop_rec if self._drop_on else None
         Fx.set_dropout(drop)            # restarts the site ordinals of this forward
         try:
             if self.spec.kind == "image":
@@ -194,7 +199,34 @@ class Trainer:
         self.dropout = p
         if hasattr(self.model, "dropout"):
             self.model.dropout = p or 0.0
-        if p is not None and self._drop_rec is None:
+        self._drop_alloc()
+
+    def set_attn_dropout(self, p: Optional[float]) -> None:
+        """Dropout with probability ``p`` on the softmax probabilities inside
+        the attention kernels of a model that has an ``attn_dropout``
+        attribute (the Transformer; others ignore it). ``None`` or 0 turns it
+        off. ``p`` is quantised to 1/256: 0.1 drops 26/256. It shares the
+        device record of ``set_dropout``, which is allocated, synced and
+        advanced once per step when either knob is on. A change of ``p``
+        re-captures the step graph."""
+        if p is not None:
+            p = float(p)
+            if Fx.attn_dropout_threshold(p) == 0 or not hasattr(self.model, "attn_dropout"):
+                p = None
+        if p != self.attn_dropout:
+            self._graph = None
+            self._g_loss = None
+        self.attn_dropout = p
+        if hasattr(self.model, "attn_dropout"):
+            self.model.attn_dropout = p or 0.0
+        self._drop_alloc()
+
+    @property
+    def _drop_on(self) -> bool:
+        return bool(self.dropout or self.attn_dropout)
+
+    def _drop_alloc(self) -> None:
+        if self._drop_on and self._drop_rec is None:
             self._drop_rec = torch.zeros(4, dtype=torch.int32, device=self.device)
             self._drop_at = None
 
@@ -203,7 +235,7 @@ class Trainer:
         step_count). A host compare per step; a write only after
         construction, ``reset``, a restore / P2P receive that set
         ``step_count``, or a ``rebind`` to another gang position."""
-        if not self.dropout:
+        if not self._drop_on:
             return
         want = (int(self.seed) & 0xFFFFFFFF, comm_rank(self.group) & 0xFFFFFFFF, int(self.step_count) & 0xFFFFFFFF)
         if want != self._drop_at:
@@ -415,7 +447,7 @@ class Trainer:
             torch.cuda.current_stream(self.device).wait_event(self._ready)
             self._ready = None
         self._drop_sync()
-        if self._drop_at is not None and self.dropout:
+        if self._drop_at is not None and self._drop_on:
             # what the record holds once this step's advance has run
             self._drop_at = self._drop_at[:2] + ((self._drop_at[2] + 1) & 0xFFFFFFFF,)
         if self.use_graph and self._graph is None and self._warm < 2:

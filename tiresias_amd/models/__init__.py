@@ -49,6 +49,9 @@ class ModelSpec:
     # (Trainer.set_dropout); None = off. No shipped model sets it: a job asks
     # for it (--dropout)
     dropout: Optional[float] = None
+    # attention-probability dropout of the job's recipe (Trainer.set_attn_dropout,
+    # --attn-dropout); None = off. Models without the attribute ignore it
+    attn_dropout: Optional[float] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

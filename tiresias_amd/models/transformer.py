@@ -17,8 +17,12 @@ sub-layer output -- each pending residual, the ones the final ``enc_ln`` /
 ``dec_ln`` add included -- is dropped out inside the fused add + LayerNorm
 kernels, and the two embedded inputs through the standalone kernel. Masks are
 regenerated in the backward, never stored (ops/functional.py "dropout").
-Attention-probability dropout is out of scope: the paper's P_drop does not
-include it, and it would need changes to the attention kernels.
+Attention-probability dropout (``attn_dropout=p``, off by default, a knob of
+its own: the paper's P_drop does not include it, most framework recipes do)
+drops softmax probabilities inside the attention kernels of the encoder
+self-attention, the decoder self-attention and the decoder cross-attention;
+p is quantised to 1/256 and the mask is regenerated in the attention backward
+(ops/functional.py "dropout", csrc/include/tam/philox.h).
 """
 from __future__ import annotations
 
@@ -35,7 +39,7 @@ class TransformerBase:
 
     def __init__(self, arena: Arena, vocab: int = 32000, d: int = 512, heads: int = 8,
                  ffn: int = 2048, enc_layers: int = 6, dec_layers: int = 6, max_len: int = 1024,
-                 dropout: float = 0.0):
+                 dropout: float = 0.0, attn_dropout: float = 0.0):
         assert d == heads * 64, "kernels are built for head_dim 64"
         A = arena
         self.arena, self.d, self.h, self.vocab = arena, d, heads, vocab
@@ -74,10 +78,18 @@ class TransformerBase:
         self.dec_ln = ln("dec.ln")
         self.training = True
         self.dropout = dropout
+        self.attn_dropout = attn_dropout
 
     @property
     def _p(self):
         return self.dropout if (self.training and self.dropout and self.dropout > 0) else None
+
+    @property
+    def _pa(self):
+        """Keyword arguments of an attention call: ``drop=p`` while training
+        with attention dropout on, nothing otherwise (the call as it was)."""
+        on = self.training and self.attn_dropout and self.attn_dropout > 0
+        return {"drop": self.attn_dropout} if on else {}
 
     @staticmethod
     def _sinusoid(n, d, dev):
@@ -117,7 +129,7 @@ class TransformerBase:
         for L in self.enc:
             x, h = self._ln_skip(x, r, L["ln1"])
             qkv = Fx.linear(h, *L["qkv"])
-            a = Fx.self_attention(qkv, self.h, causal=False)
+            a = Fx.self_attention(qkv, self.h, causal=False, **self._pa)
             r = Fx.linear(a, *L["o"])
             x, r = self._ffn(x, r, L)
         return self._ln_skip(x, r, self.enc_ln)[1]
@@ -129,11 +141,11 @@ class TransformerBase:
         hold = {"n": 0}
         for i, L in enumerate(self.dec):
             x, h = self._ln_skip(x, r, L["ln1"])
-            a = Fx.self_attention(Fx.linear(h, *L["qkv"]), self.h, causal=True)
+            a = Fx.self_attention(Fx.linear(h, *L["qkv"]), self.h, causal=True, **self._pa)
             x, h = self._ln_skip(x, Fx.linear(a, *L["o"]), L["ln2"])
             q = Fx.linear(h, *L["q"])
             a = Fx.cross_attention(q, kv_all, self.h, k_slot=2 * i, v_slot=2 * i + 1, nkv=2 * n,
-                                   kv_hold=hold)
+                                   kv_hold=hold, **self._pa)
             x, r = self._ffn(x, Fx.linear(a, *L["o2"]), L)
         x = self._ln_skip(x, r, self.dec_ln)[1]
         return Fx.linear(x, self.emb)   # tied output projection -> logits

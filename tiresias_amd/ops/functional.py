@@ -821,17 +821,58 @@ def dropout_mask(n: int, site: int, seed: int, stream: int, step: int, thr: int)
     return u.reshape(-1)[:n] >= thr
 
 
+# Attention-probability dropout (inside the attention kernels): the mask is a
+# pure function of the logical position (b, h, q, kv) in the [B,H,Sq,Sk]
+# probability tensor. One Philox call covers 4 queries x 4 keys, block (Q, K) =
+# (q >> 2, kv >> 2): counter (K | (Q << 16), b*H + h, 0x80000000 | a, step), key
+# (seed, stream), u = (out[q & 3] >> (8 * (kv & 3))) & 0xff, kept iff u >= thr
+# with thr = round(p * 256); kept probabilities are scaled by fp32(256) /
+# fp32(256 - thr). a is the attention call's ordinal within the forward, from a
+# counter of its own, so the elementwise sites keep their ordinals whether or
+# not attention dropout is on. The LSE is that of the undropped scores.
+def attn_dropout_threshold(p: float) -> int:
+    """thr = round(p * 256): p is quantised to 1/256 (0.1 drops 26/256); 0
+    means no attention dropout."""
+    p = float(p)
+    thr = int(round(p * 256.0)) if p == p else -1
+    if not (0.0 <= p < 1.0 and 0 <= thr < 256):
+        raise ValueError(f"attn_dropout must satisfy 0 <= p < 1 with round(p * 256) < 256, got {p}")
+    return thr
+
+
+def attn_dropout_scale(thr: int) -> float:
+    """fp32(256) / fp32(256 - thr), one fp32 division, as a Python float."""
+    return float(torch.tensor(256.0, dtype=torch.float32) / torch.tensor(float(256 - thr), dtype=torch.float32))
+
+
+def attn_dropout_mask(B: int, H: int, Sq: int, Sk: int, site: int, seed: int, stream: int, step: int,
+                      thr: int) -> torch.Tensor:
+    """Keep mask (bool [B,H,Sq,Sk], CPU) of attention call ``site``."""
+    nq, nk = (Sq + 3) // 4, (Sk + 3) // 4
+    Q = torch.arange(nq, dtype=torch.int64)[None, :, None]
+    K = torch.arange(nk, dtype=torch.int64)[None, None, :]
+    bh = torch.arange(B * H, dtype=torch.int64)[:, None, None]
+    c0 = ((K | (Q << 16)) & _M32).expand(B * H, nq, nk)
+    o = philox4x32_10(c0, bh.expand_as(c0), torch.full_like(c0, 0x80000000 | (site & 0x7FFFFFFF)),
+                      torch.full_like(c0, step & _M32), seed & _M32, stream & _M32)
+    w = torch.stack(o, 2)                                                   # [BH, nq, 4 (q & 3), nk]
+    u = torch.stack([(w >> (8 * j)) & 0xFF for j in range(4)], 4)          # [BH, nq, 4, nk, 4 (kv & 3)]
+    return (u.reshape(B, H, 4 * nq, 4 * nk)[:, :, :Sq, :Sk] >= thr).contiguous()
+
+
 _DROP_REC: Optional[torch.Tensor] = None
 _DROP_SITE = 0
+_ATTN_DROP_SITE = 0
 
 
 def set_dropout(rec: Optional[torch.Tensor]) -> None:
     """Install a trainer's dropout record for the forward + backward that
     follows (None: dropout calls are the identity) and restart the site
     ordinals. The trainer does this at the start of every ``_fwd_bwd``."""
-    global _DROP_REC, _DROP_SITE
+    global _DROP_REC, _DROP_SITE, _ATTN_DROP_SITE
     _DROP_REC = rec
     _DROP_SITE = 0
+    _ATTN_DROP_SITE = 0
 
 
 def _drop_args(p: Optional[float]):
@@ -846,6 +887,21 @@ def _drop_args(p: Optional[float]):
     site = _DROP_SITE
     _DROP_SITE += 1
     return (_DROP_REC, site, thr, dropout_scale(thr))
+
+
+def _attn_drop_args(p: Optional[float]):
+    """(rec, site, thr, scale) of the next attention call's probability
+    dropout, or None when it has none (p None / 0 / below 1/512, or no record
+    installed). The ordinals are the attention calls' own."""
+    global _ATTN_DROP_SITE
+    if p is None or _DROP_REC is None or not p:
+        return None
+    thr = attn_dropout_threshold(p)
+    if thr == 0:
+        return None
+    site = _ATTN_DROP_SITE
+    _ATTN_DROP_SITE += 1
+    return (_DROP_REC, site, thr, attn_dropout_scale(thr))
 
 
 def _cpu_keep(x: torch.Tensor, drop) -> torch.Tensor:
@@ -1259,8 +1315,9 @@ def embedding(ids: torch.Tensor, table: Param, scale: float = 1.0, time_major: b
 
 
 # ============================================================ attention
-def _attn_ref(q, k, v, causal, scale, kv_len):
+def _attn_ref(q, k, v, causal, scale, kv_len, drop=None):
     # q [B,Sq,H,64], k/v [B,Sk,H,64] -> o [B,Sq,H,64], lse [B,H,Sq]
+    # drop = (record, site, thr, scale): the kernels' probability mask
     qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
     s = qf @ kf.transpose(-1, -2) * scale
     Sq, Sk = s.shape[-2], s.shape[-1]
@@ -1273,6 +1330,12 @@ def _attn_ref(q, k, v, causal, scale, kv_len):
         s = s.masked_fill(km[:, None, None, :], float("-inf"))
     lse = torch.logsumexp(s, -1)
     p = torch.exp(s - lse[..., None])
+    if drop is not None:
+        rec, site, thr, dscale = drop
+        seed, stream, step = (int(x) for x in rec[:3].tolist())
+        keep = attn_dropout_mask(s.shape[0], s.shape[1], Sq, Sk, site, seed, stream, step, thr)
+        p = torch.where(keep.to(p.device), p, torch.zeros((), dtype=p.dtype, device=p.device)) * \
+            torch.tensor(dscale, dtype=torch.float32, device=p.device)
     o = (p @ vf).permute(0, 2, 1, 3)
     return o, lse
 
@@ -1280,16 +1343,20 @@ def _attn_ref(q, k, v, causal, scale, kv_len):
 class _Attn(Function):
     """q_src: [B,Sq,nq*H*64], kv_src: [B,Sk,nkv*H*64]; q at slot q_slot of q_src,
     k / v at slots k_slot / v_slot of kv_src (self-attention passes the same
-    packed qkv tensor for both, slots 0/1/2). Gradients come back packed."""
+    packed qkv tensor for both, slots 0/1/2). Gradients come back packed.
+    drop = (record, site, thr, scale) from _attn_drop_args: dropout on the
+    softmax probabilities inside the kernels, O = (keep * P) V * scale; the
+    backward regenerates the mask from the same tuple."""
 
     @staticmethod
     def forward(ctx, q_src, kv_src, H: int, q_slot: int, nq: int, k_slot: int, v_slot: int,
-                nkv: int, causal: bool, kv_len, kv_hold=None, tm: bool = False):
+                nkv: int, causal: bool, kv_len, kv_hold=None, tm: bool = False, drop=None):
         # tm: q_src / kv_src / the output are time-major [S,B,.] (GNMT's
         # recurrent layout); the kernels take batch and token strides, so the
         # [B,S,H,64] views are transposes and no layout copy is made
         same = q_src is kv_src
         ctx.tm = tm
+        ctx.drop = drop
         # kv_hold: several attention calls read different slots of ONE packed
         # K/V tensor (the decoder's batched cross-attention projection); they
         # write their slots into one shared gradient buffer and only the call
@@ -1307,9 +1374,9 @@ class _Attn(Function):
             ob = torch.empty((Sq, B, H, 64) if tm else (B, Sq, H, 64), dtype=BF16, device=q_src.device)
             o = ob.transpose(0, 1) if tm else ob
             lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q_src.device)
-            _T().attn_forward(qv, kv_, vv, o, lse, causal, scale, kv_len)
+            _T().attn_forward(qv, kv_, vv, o, lse, causal, scale, kv_len, *(drop or ()))
         else:
-            of, lse = _attn_ref(qv, kv_, vv, causal, scale, kv_len)
+            of, lse = _attn_ref(qv, kv_, vv, causal, scale, kv_len, drop)
             ob = (of.transpose(0, 1) if tm else of).to(BF16).contiguous()
         ctx.cfg = (same, H, q_slot, nq, k_slot, v_slot, nkv, causal, scale)
         ctx.save_for_backward(q_src, kv_src, ob, lse, kv_len)
@@ -1342,22 +1409,22 @@ class _Attn(Function):
             delta = torch.empty(B, H, Sq, dtype=torch.float32, device=q_src.device)
             _T().attn_backward(qv, kvv[:, :, k_slot], kvv[:, :, v_slot], o, do, lse, dqv,
                                dkvv[:, :, k_slot], dkvv[:, :, v_slot], dq_acc, delta, causal, scale,
-                               kv_len)
+                               kv_len, *(ctx.drop or ()))
         else:
             qf = qv.float().requires_grad_(True)
             kf = kvv[:, :, k_slot].float().requires_grad_(True)
             vf = kvv[:, :, v_slot].float().requires_grad_(True)
             with torch.enable_grad():
-                of, _ = _attn_ref(qf, kf, vf, causal, scale, kv_len)
+                of, _ = _attn_ref(qf, kf, vf, causal, scale, kv_len, ctx.drop)
                 gq, gk, gv = torch.autograd.grad(of, [qf, kf, vf], do.float())
             dqv.copy_(gq.to(BF16))
             dkvv[:, :, k_slot].copy_(gk.to(BF16))
             dkvv[:, :, v_slot].copy_(gv.to(BF16))
         if same:
-            return dq_src, None, None, None, None, None, None, None, None, None, None, None
+            return dq_src, None, None, None, None, None, None, None, None, None, None, None, None
         if hold is not None and ctx.kv_idx != 0:
             dkv_src = None                 # slots written; the first caller returns the buffer
-        return dq_src, dkv_src, None, None, None, None, None, None, None, None, None, None
+        return dq_src, dkv_src, None, None, None, None, None, None, None, None, None, None, None
 
 
 def _attn_views(q_src, kv_src, H, nq, nkv, q_slot, tm):
@@ -1377,22 +1444,27 @@ def _attn_views(q_src, kv_src, H, nq, nkv, q_slot, tm):
 
 
 def self_attention(qkv: torch.Tensor, heads: int, causal: bool = False,
-                   kv_len: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """qkv: [B,S,3*H*64] packed projection output -> [B,S,H*64]."""
+                   kv_len: Optional[torch.Tensor] = None, drop: Optional[float] = None) -> torch.Tensor:
+    """qkv: [B,S,3*H*64] packed projection output -> [B,S,H*64]. drop:
+    dropout probability on the softmax probabilities (quantised to 1/256;
+    needs an installed record, see ``set_dropout``)."""
     qkv = qkv.contiguous()
-    return _Attn.apply(qkv, qkv, heads, 0, 3, 1, 2, 3, causal, kv_len, None)
+    return _Attn.apply(qkv, qkv, heads, 0, 3, 1, 2, 3, causal, kv_len, None, False, _attn_drop_args(drop))
 
 
 def cross_attention(q: torch.Tensor, kv: torch.Tensor, heads: int,
                     kv_len: Optional[torch.Tensor] = None, k_slot: int = 0, v_slot: int = 1,
-                    nkv: int = 2, kv_hold: Optional[dict] = None, time_major: bool = False) -> torch.Tensor:
+                    nkv: int = 2, kv_hold: Optional[dict] = None, time_major: bool = False,
+                    drop: Optional[float] = None) -> torch.Tensor:
     """q: [B,Sq,H*64], kv: [B,Sk,nkv*H*64] (K at slot k_slot, V at v_slot)
     -> [B,Sq,H*64]; time_major: q [Sq,B,.], kv [Sk,B,.] -> [Sq,B,H*64] with
     no layout copies. Calls sharing one packed kv pass the same ``kv_hold``
-    dict (``{"n": 0}``, fresh per forward); see _Attn."""
+    dict (``{"n": 0}``, fresh per forward); see _Attn. drop: as in
+    ``self_attention``."""
     if time_major:
         q, kv = q.contiguous(), kv.contiguous()
-    return _Attn.apply(q, kv, heads, 0, 1, k_slot, v_slot, nkv, False, kv_len, kv_hold, time_major)
+    return _Attn.apply(q, kv, heads, 0, 1, k_slot, v_slot, nkv, False, kv_len, kv_hold, time_major,
+                       _attn_drop_args(drop))
 
 
 # ============================================================ residual add
