@@ -1203,6 +1203,45 @@ void adam_op(const Tensor& w, const Tensor& g, const Tensor& m, const Tensor& v,
                  (int)step, (float)gscale, zero_grad, cur_stream(w), guard_ptr(guard, w), (long)zero_from,
                  (long)wd_until, clip_ptr(clip, w));
 }
+// bf16 optimizer state (optim.hip): m / v / mom are bfloat16, stored with
+// Philox stochastic rounding keyed by (seed, step) and indexed from `base`,
+// the arena index of element 0 of these views
+static void check_bf16s(const Tensor& w, const Tensor& g, const Tensor& wb, std::initializer_list<const Tensor*> st,
+                        int64_t step, int64_t base, int64_t zero_from, int64_t wd_until, const char* op) {
+  check_f32(w, "w"); check_f32(g, "g"); check_bf16(wb, "wb");
+  check_contig(w, "w"); check_contig(g, "g"); check_contig(wb, "wb");
+  TORCH_CHECK(w.numel() % 4 == 0 && g.numel() == w.numel() && wb.numel() == w.numel(), op, ": sizes");
+  TORCH_CHECK(((((uintptr_t)w.data_ptr()) | ((uintptr_t)g.data_ptr())) & 15) == 0 &&
+                  (((uintptr_t)wb.data_ptr()) & 7) == 0, op, ": w / g must be 16-B aligned, wb 8-B aligned");
+  for (const Tensor* t : st) {
+    check_bf16(*t, "state"); check_contig(*t, "state");
+    TORCH_CHECK(t->numel() == w.numel() && (((uintptr_t)t->data_ptr()) & 7) == 0 && t->device() == w.device(), op,
+                ": state must be a bfloat16 tensor of w's size on its device, 8-B aligned");
+  }
+  TORCH_CHECK(zero_from % 4 == 0 && (wd_until < 0 || wd_until % 4 == 0), op, ": region bounds % 4");
+  TORCH_CHECK(base >= 0 && base % 4 == 0, op, ": base must be a non-negative multiple of 4, got ", base);
+  TORCH_CHECK(step >= 1 && step <= 0x7fffffffLL, op, ": step must be a 1-based optimizer step, got ", step);
+}
+void sgd_bf16s_op(const Tensor& w, const Tensor& g, const Tensor& mom, const Tensor& wb, double lr, double momentum,
+                  double wd, double gscale, bool nesterov, bool zero_grad, int64_t seed, int64_t step, int64_t base,
+                  const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until,
+                  const optional<Tensor>& clip) {
+  check_bf16s(w, g, wb, {&mom}, step, base, zero_from, wd_until, "tam.sgd_step_bf16s");
+  tam::sgd_step_bf16s(w.data_ptr<float>(), g.data_ptr<float>(), bpm(mom), bpm(wb), w.numel(), (float)lr,
+                      (float)momentum, (float)wd, (float)gscale, nesterov, zero_grad, (unsigned)(uint64_t)seed,
+                      (unsigned)step, (long)base, cur_stream(w), guard_ptr(guard, w), (long)zero_from,
+                      (long)wd_until, clip_ptr(clip, w));
+}
+void adam_bf16s_op(const Tensor& w, const Tensor& g, const Tensor& m, const Tensor& v, const Tensor& wb, double lr,
+                   double b1, double b2, double eps, double wd, int64_t step, double gscale, bool zero_grad,
+                   int64_t seed, int64_t base, const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until,
+                   const optional<Tensor>& clip) {
+  check_bf16s(w, g, wb, {&m, &v}, step, base, zero_from, wd_until, "tam.adam_step_bf16s");
+  tam::adam_step_bf16s(w.data_ptr<float>(), g.data_ptr<float>(), bpm(m), bpm(v), bpm(wb), w.numel(), (float)lr,
+                       (float)b1, (float)b2, (float)eps, (float)wd, (int)step, (float)gscale, zero_grad,
+                       (unsigned)(uint64_t)seed, (long)base, cur_stream(w), guard_ptr(guard, w), (long)zero_from,
+                       (long)wd_until, clip_ptr(clip, w));
+}
 // global-norm gradient clip (optim.hip): g -> one fp64 partial per block ->
 // the clip record the optimizer steps take
 void grad_sumsq_op(const Tensor& g, const Tensor& partials) {
@@ -1486,6 +1525,8 @@ TORCH_LIBRARY(tam, m) {
   m.def("cast_f32_bf16(Tensor x, Tensor(a!) y) -> ()", &cast_op);
   m.def("sgd_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &sgd_op);
   m.def("adam_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adam_op);
+  m.def("sgd_step_bf16s(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, int seed, int step, int base=0, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &sgd_bf16s_op);
+  m.def("adam_step_bf16s(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, int seed, int base=0, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adam_bf16s_op);
   m.def("grad_sumsq(Tensor g, Tensor(a!) partials) -> ()", &grad_sumsq_op);
   m.def("grad_clip_finalize(Tensor partials, float max_norm, float gscale, Tensor(a!) clip) -> ()", &grad_clip_finalize_op);
   m.def("grad_sumsq_blocks(int n) -> int", &grad_sumsq_blocks_op);

@@ -147,6 +147,20 @@ void adam_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float
                float b2, float eps, float wd, int step, float gscale, int zero_grad,
                hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
                const float* clip = nullptr);
+// bf16 optimizer state: the same steps with the moments kept in bf16 and
+// stored with Philox stochastic rounding (contract in tam/philox.h). The
+// weights and the shadow come from the unrounded fp32 moments. seed: the job's
+// seed; step: the 1-based optimizer step (for SGD too); base (% 4 == 0): arena
+// index of element 0 of this launch, so a launch over a slice draws what one
+// launch over the whole arena draws
+void sgd_step_bf16s(float* w, float* g, bf16_t* mom, bf16_t* wb, long n, float lr, float momentum, float wd,
+                    float gscale, int nesterov, int zero_grad, unsigned seed, unsigned step, long base,
+                    hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+                    const float* clip = nullptr);
+void adam_step_bf16s(float* w, float* g, bf16_t* m, bf16_t* v, bf16_t* wb, long n, float lr, float b1, float b2,
+                     float eps, float wd, int step, float gscale, int zero_grad, unsigned seed, long base,
+                     hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+                     const float* clip = nullptr);
 // global-norm gradient clip: grad_sumsq writes one fp64 partial per block and
 // zeroes partials[blocks..slots); grad_clip_finalize sums them and writes the
 // 16-B clip record {float scale, float norm, u32 non-finite steps, u32

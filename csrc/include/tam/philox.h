@@ -29,6 +29,25 @@
 // of one key (one byte of each of the four words), so either direction eats
 // whole Philox outputs. The running max, row sum and LSE come from the
 // undropped scores: O = (keep * P) V * scale, LSE unchanged.
+//
+// Optimizer-state rounding contract (README "bf16 optimizer state"; tests
+// rebuild it on the host): bf16 moments are stored with stochastic rounding.
+// One Philox call covers 4 consecutive arena elements, the float4 group the
+// optimizer kernels work in. For arena element index e (within the whole
+// arena, not within the launch): q = e >> 2, j = e & 3,
+//   counter = (q & 0xffffffff, q >> 32, 0x40000000, step), key = (seed, 0),
+//   u_m = out[j] & 0xffff   (first moment / SGD momentum),
+//   u_v = out[j] >> 16      (Adam second moment).
+// step is the 1-based optimizer step (the integer Adam takes). The site word
+// 0x40000000 keeps this counter space apart from elementwise dropout (small
+// ordinals) and attention dropout (top bit set). The key holds no gang
+// position: every member of a non-sharded gang writes identical state.
+// Rounding fp32 bits b with a 16-bit draw u (sr_bf16): exponent field not all
+// ones -> (b + u) >> 16, which rounds the magnitude up with probability
+// (b & 0xffff) / 65536 -- unbiased, and a carry into the exponent (up to inf
+// from the largest finite values) is the correct result; inf passes through;
+// NaN stays NaN (quiet bit forced). A value that is exact in bf16 (low 16
+// bits zero) comes back unchanged for every draw.
 #pragma once
 #include <stdint.h>
 
@@ -81,6 +100,25 @@ TAM_HD uint32_t drop_keep8(uint64_t q, uint32_t site, const DropRec& r, uint32_t
     bits |= ((o[i] >> 16) >= thr ? 1u : 0u) << (2 * i + 1);
   }
   return bits;
+}
+
+// site word of the optimizer-state rounding draws
+constexpr uint32_t kOptStateSite = 0x40000000u;
+
+// fp32 bits b -> bf16 bits, stochastically rounded with the 16-bit draw u
+TAM_HD uint32_t sr_bf16(uint32_t b, uint32_t u) {
+  if ((b & 0x7f800000u) == 0x7f800000u)   // inf passes, NaN keeps its sign and turns quiet
+    return (b >> 16) | ((b & 0x007fffffu) ? 0x40u : 0u);
+  return (b + u) >> 16;
+}
+
+// the four words of group q (arena elements 4q .. 4q+3) at optimizer step
+// `step`: element j rounds its first moment with out[j] & 0xffff and its
+// second moment with out[j] >> 16
+TAM_HD void opt_state_draw4(uint64_t q, uint32_t seed, uint32_t step, uint32_t (&out)[4]) {
+  const uint32_t ctr[4] = {(uint32_t)q, (uint32_t)(q >> 32), kOptStateSite, step};
+  const uint32_t key[2] = {seed, 0u};
+  philox4x32_10(ctr, key, out);
 }
 
 // the four words of attention-mask block (Q, K) = (q >> 2, kv >> 2) of head

@@ -25,6 +25,7 @@
 
 #include "tam/common.h"
 #include "tam/kernels.h"
+#include "tam/philox.h"
 
 namespace tam {
 
@@ -215,6 +216,157 @@ __global__ void __launch_bounds__(256) sgd_stream_kernel(float* __restrict__ w, 
   for (long i = full + t; i < n4; i += stride) body(i, ld4<1, NT>(w, i), ld4<1, NT>(g, i), ld4<1, NT>(mom, i));
 }
 
+// ------------------------------------------------------ bf16 optimizer state
+// Siblings of the two streaming kernels above for a job that keeps its
+// moments in bf16 (Trainer opt_dtype="bf16"): m / v / mom are bf16, 8 B per
+// float4 group, widened by a shift; the element update is the same explicit
+// FMA sequence on fp32 values, and the weight and the shadow come from the
+// fresh UNROUNDED moments, so for state that is exact in bf16 a step writes
+// the weights the fp32-state kernel writes. Only the stored moments are
+// rounded, stochastically (tam/philox.h "Optimizer-state rounding
+// contract"): one Philox call per group, keyed by the job's seed and the
+// optimizer step, indexed by the group's position in the WHOLE arena (q0 =
+// arena index of this launch's element 0, / 4), so a launch over [lo, hi)
+// draws what one launch over the arena draws. Nothing random is stored. The
+// draws of an unrolled pass are computed after its loads are issued and
+// depend on none of them: the integer work runs under the load latency.
+// The guard / non-finite-clip path writes no state and draws nothing.
+template <bool NT>
+__device__ __forceinline__ uint2 ld2(const bf16_t* p, long i) {
+  if constexpr (NT) {
+    const u32x2_t r = __builtin_nontemporal_load((const u32x2_t*)p + i);
+    return make_uint2(r[0], r[1]);
+  } else {
+    return ((const uint2*)p)[i];
+  }
+}
+__device__ __forceinline__ float4 widen4(uint2 s) {
+  return make_float4(__uint_as_float(s.x << 16), __uint_as_float(s.x & 0xffff0000u), __uint_as_float(s.y << 16),
+                     __uint_as_float(s.y & 0xffff0000u));
+}
+struct Draw4 {
+  uint32_t r[4];
+};
+__device__ __forceinline__ Draw4 draw4(long q, uint32_t seed, uint32_t step) {
+  Draw4 d;
+  opt_state_draw4((uint64_t)q, seed, step, d.r);
+  return d;
+}
+// HI = false: the low halves of the draw words (first moment / momentum),
+// true: the high halves (second moment)
+template <bool HI>
+__device__ __forceinline__ uint2 round4(float4 f, const Draw4& d) {
+  const float* fp = (const float*)&f;
+  uint32_t o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = sr_bf16(__float_as_uint(fp[j]), HI ? d.r[j] >> 16 : d.r[j] & 0xffffu);
+  return make_uint2(o[0] | (o[1] << 16), o[2] | (o[3] << 16));
+}
+
+template <int U, bool NT>
+__global__ void __launch_bounds__(256) adam_stream_bf16s_kernel(
+    float* __restrict__ w, float* __restrict__ g, bf16_t* __restrict__ m, bf16_t* __restrict__ v,
+    bf16_t* __restrict__ wb, long n4, float lr, float b1, float b2, float eps, float wd0, float bc1, float bc2,
+    float gscale, int zero_grad, const unsigned* guard, long zero_from4, long wd_until4, const float* clip,
+    uint32_t seed, uint32_t step, long q0) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  if ((guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f)) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride)
+      if (i >= zero_from4) st4<NT>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  if (clip != nullptr) gscale *= clip[0];
+  const float ib1 = 1.f / bc1, ib2 = 1.f / bc2;
+  auto body = [&](long i, float4 wv, float4 gv, uint2 ms, uint2 vs, const Draw4& d) {
+    float4 mv = widen4(ms), vv = widen4(vs);
+    float* wp = (float*)&wv; float* gp = (float*)&gv; float* mp = (float*)&mv; float* vp = (float*)&vv;
+    const float wd = i < wd_until4 ? wd0 : 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gr = gp[k] * gscale;
+      mp[k] = __builtin_fmaf(b1, mp[k], (1.f - b1) * gr);
+      vp[k] = __builtin_fmaf(b2, vp[k], (1.f - b2) * gr * gr);
+      const float mh = mp[k] * ib1, vh = vp[k] * ib2;
+      const float u = __builtin_fmaf(wd, wp[k], mh / (sqrtf(vh) + eps));   // decoupled (AdamW)
+      wp[k] = __builtin_fmaf(-lr, u, wp[k]);
+    }
+    st4<NT>(w, i, wv); st2<NT>(m, i, round4<false>(mv, d)); st2<NT>(v, i, round4<true>(vv, d));
+    if (zero_grad && i >= zero_from4) st4<NT>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
+    st2<NT>(wb, i, make_uint2(pack_bf2(wp[0], wp[1]), pack_bf2(wp[2], wp[3])));
+  };
+  const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long full = n4 / (U * stride) * (U * stride);
+  for (long base = t; base < full; base += U * stride) {
+    float4 wv[U], gv[U];
+    uint2 ms[U], vs[U];
+    Draw4 d[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = base + u * stride;
+      wv[u] = ld4<U, NT>(w, i); gv[u] = ld4<U, NT>(g, i); ms[u] = ld2<NT>(m, i); vs[u] = ld2<NT>(v, i);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) d[u] = draw4(q0 + base + u * stride, seed, step);
+#pragma unroll
+    for (int u = 0; u < U; ++u) body(base + u * stride, wv[u], gv[u], ms[u], vs[u], d[u]);
+  }
+  for (long i = full + t; i < n4; i += stride) {
+    const float4 wv = ld4<1, NT>(w, i), gv = ld4<1, NT>(g, i);
+    const uint2 ms = ld2<NT>(m, i), vs = ld2<NT>(v, i);
+    body(i, wv, gv, ms, vs, draw4(q0 + i, seed, step));
+  }
+}
+
+template <int U, bool NT>
+__global__ void __launch_bounds__(256) sgd_stream_bf16s_kernel(
+    float* __restrict__ w, float* __restrict__ g, bf16_t* __restrict__ mom, bf16_t* __restrict__ wb, long n4,
+    float lr, float momentum, float wd0, float gscale, int nesterov, int zero_grad, const unsigned* guard,
+    long zero_from4, long wd_until4, const float* clip, uint32_t seed, uint32_t step, long q0) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  if ((guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f)) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride)
+      if (i >= zero_from4) st4<NT>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  if (clip != nullptr) gscale *= clip[0];
+  auto body = [&](long i, float4 wv, float4 gv, uint2 ms, const Draw4& dr) {
+    float4 mv = widen4(ms);
+    float* wp = (float*)&wv; float* gp = (float*)&gv; float* mp = (float*)&mv;
+    const float wd = i < wd_until4 ? wd0 : 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float d = __builtin_fmaf(wd, wp[k], gp[k] * gscale);
+      mp[k] = __builtin_fmaf(momentum, mp[k], d);
+      d = nesterov ? __builtin_fmaf(momentum, mp[k], d) : mp[k];
+      wp[k] = __builtin_fmaf(-lr, d, wp[k]);
+    }
+    st4<NT>(w, i, wv); st2<NT>(mom, i, round4<false>(mv, dr));
+    if (zero_grad && i >= zero_from4) st4<NT>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
+    st2<NT>(wb, i, make_uint2(pack_bf2(wp[0], wp[1]), pack_bf2(wp[2], wp[3])));
+  };
+  const long t = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  const long full = n4 / (U * stride) * (U * stride);
+  for (long base = t; base < full; base += U * stride) {
+    float4 wv[U], gv[U];
+    uint2 ms[U];
+    Draw4 d[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = base + u * stride;
+      wv[u] = ld4<U, NT>(w, i); gv[u] = ld4<U, NT>(g, i); ms[u] = ld2<NT>(mom, i);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) d[u] = draw4(q0 + base + u * stride, seed, step);
+#pragma unroll
+    for (int u = 0; u < U; ++u) body(base + u * stride, wv[u], gv[u], ms[u], d[u]);
+  }
+  for (long i = full + t; i < n4; i += stride) {
+    const float4 wv = ld4<1, NT>(w, i), gv = ld4<1, NT>(g, i);
+    const uint2 ms = ld2<NT>(mom, i);
+    body(i, wv, gv, ms, draw4(q0 + i, seed, step));
+  }
+}
+
 // 0: adam_kernel / sgd_kernel (one group per thread per iteration); 3: U=4
 // + NT (1 / 2, U=2 with / without NT, measured between the two and were
 // dropped). -1 (default): optim_pick.
@@ -300,6 +452,29 @@ void adam_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float
       hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, s, w, g, m, v, wb, n / 4, lr, b1, b2, eps, wd, bc1, bc2,
                          gscale, zero_grad, guard, zf4, wu4, clip);
   }
+}
+
+// bf16-state steps: the streaming form only (TAM_OPTIM_VARIANT selects among
+// the fp32-state kernels). base (elements, % 4 == 0): arena index of element 0
+// of this launch; step: the 1-based optimizer step, for SGD too (it indexes
+// the rounding draws).
+void sgd_step_bf16s(float* w, float* g, bf16_t* mom, bf16_t* wb, long n, float lr, float momentum, float wd,
+                    float gscale, int nesterov, int zero_grad, unsigned seed, unsigned step, long base,
+                    hipStream_t s, const unsigned* guard, long zero_from, long wd_until, const float* clip) {
+  const dim3 grid(ogrid(n / 4));
+  const long zf4 = zero_from / 4, wu4 = wd_until < 0 ? n / 4 : wd_until / 4;
+  hipLaunchKernelGGL((sgd_stream_bf16s_kernel<4, true>), grid, dim3(256), 0, s, w, g, mom, wb, n / 4, lr, momentum,
+                     wd, gscale, nesterov, zero_grad, guard, zf4, wu4, clip, seed, step, base / 4);
+}
+
+void adam_step_bf16s(float* w, float* g, bf16_t* m, bf16_t* v, bf16_t* wb, long n, float lr, float b1, float b2,
+                     float eps, float wd, int step, float gscale, int zero_grad, unsigned seed, long base,
+                     hipStream_t s, const unsigned* guard, long zero_from, long wd_until, const float* clip) {
+  const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+  const dim3 grid(ogrid(n / 4));
+  const long zf4 = zero_from / 4, wu4 = wd_until < 0 ? n / 4 : wd_until / 4;
+  hipLaunchKernelGGL((adam_stream_bf16s_kernel<4, true>), grid, dim3(256), 0, s, w, g, m, v, wb, n / 4, lr, b1, b2,
+                     eps, wd, bc1, bc2, gscale, zero_grad, guard, zf4, wu4, clip, seed, (unsigned)step, base / 4);
 }
 
 // ------------------------------------------------- global-norm gradient clip

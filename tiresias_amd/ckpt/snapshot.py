@@ -156,6 +156,14 @@ def load_snapshot(path: str, trainer) -> int:
     d = torch.load(path, map_location="cpu", weights_only=True)
     st = trainer.state_tensors()
     for k, v in d["state"].items():
+        # a snapshot of the other optimizer-state format (Trainer opt_dtype)
+        # is refused before anything is written: neither a silent cast nor a
+        # reinterpretation of its bytes
+        if k in st and (v.dtype != st[k].dtype or v.numel() != st[k].numel()):
+            raise ValueError(f"snapshot {path}: buffer {k!r} is {v.dtype} x {v.numel()}, the trainer holds "
+                             f"{st[k].dtype} x {st[k].numel()} (a snapshot restores only into a trainer of "
+                             "the same model and opt_dtype)")
+    for k, v in d["state"].items():
         if k in st:
             st[k].copy_(v, non_blocking=False)
     A = trainer.arena

@@ -37,6 +37,10 @@ def main(argv=None) -> int:
                     help="dropout probability on the attention probabilities, inside the attention kernels "
                          "(0 <= p < 1, quantised to 1/256: 0.1 drops 26/256); models without attention "
                          "dropout ignore it")
+    ap.add_argument("--opt-dtype", choices=("fp32", "bf16"),
+                    help="format of the optimizer state: bf16 keeps the moments in bf16 with stochastic "
+                         "rounding (4 B per parameter less for Adam, 2 B for SGD, resident and spilled); "
+                         "default fp32")
     ap.add_argument("--status", action="store_true")
     ap.add_argument("--shutdown", action="store_true", help="stop serving once the cluster drains")
     a = ap.parse_args(argv)
@@ -52,7 +56,7 @@ def main(argv=None) -> int:
         ap.error("--model and one of --iterations / --duration are required")
     jid = sp.submit(a.model, a.gpus, iterations=a.iterations, duration=a.duration, job_id=a.job_id,
                     batch=a.batch, grad_clip=a.grad_clip, dropout=a.dropout,
-                    attn_dropout=a.attn_dropout)
+                    attn_dropout=a.attn_dropout, opt_dtype=a.opt_dtype)
     print(jid)
     return 0
 

@@ -50,6 +50,7 @@ class JobSpec:
     cpu_per_task: int = 12           # reference job.py:103
     mem_per_task: int = 60           # reference job.py:104
     user: str = ""
+    opt_dtype: Optional[str] = None  # optimizer-state format ("fp32" / "bf16"; None = fp32): sizes the job's state
 
     @property
     def num_workers(self) -> int:

@@ -55,7 +55,8 @@ class CkptCostModel:
         if prof is None:
             return 0.0
         opt = "adam" if job.spec.model in ("transformer", "gnmt") else "sgd"
-        return float(prof.state_bytes(opt))
+        # (a job that keeps bf16 optimizer state, JobSpec.opt_dtype, moves 2 B per moment)
+        return float(prof.state_bytes(opt, getattr(job.spec, "opt_dtype", None)))
 
     def on_preempt(self, job, alloc) -> Tuple[float, float]:
         """Returns (save seconds, bytes moved)."""

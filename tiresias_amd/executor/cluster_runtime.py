@@ -149,6 +149,7 @@ class ReplayJob:
     grad_clip: Optional[float] = None    # global-norm gradient clip of the job (None = off)
     dropout: Optional[float] = None      # training dropout of the job (None = off)
     attn_dropout: Optional[float] = None     # attention-probability dropout of the job (None = off)
+    opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" (None = fp32)
 
 
 class Controller:
@@ -510,7 +511,7 @@ class Controller:
         now = self.now()
         for req in self.spool.poll():
             try:
-                jid, model, g, iters, batch, clip, drop, adrop = self._validate(req)
+                jid, model, g, iters, batch, clip, drop, adrop, odt = self._validate(req)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -521,9 +522,9 @@ class Controller:
                     self.log.decision(now, "reject", jid or "?", reason=why)
                 continue
             spec = JobSpec(job_id=jid, submit_time=now, duration=iters * self._iter_est(model, g),
-                           num_gpu=g, model=model, iterations=iters)
+                           num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
-                                        dropout=drop, attn_dropout=adrop)
+                                        dropout=drop, attn_dropout=adrop, opt_dtype=odt)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -532,8 +533,8 @@ class Controller:
 
     def _validate(self, req: dict):
         """Untrusted spool request -> (job_id, model, num_gpu, iterations,
-        batch, grad_clip, dropout, attn_dropout); raises ValueError with the rejection
-        reason."""
+        batch, grad_clip, dropout, attn_dropout, opt_dtype); raises ValueError with
+        the rejection reason."""
         from ..models import MODELS
 
         jid = req.get("job_id")
@@ -585,7 +586,10 @@ class Controller:
                     or round(adrop * 256) >= 256):
                 raise ValueError(f"attn_dropout must be a number p with 0 <= p < 1 (quantised to 1/256), got {adrop!r}")
             adrop = float(adrop)
-        return jid, model, g, iters, batch, clip, drop, adrop
+        odt = req.get("opt_dtype")
+        if odt is not None and (not isinstance(odt, str) or odt not in ("fp32", "bf16")):
+            raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', got {odt!r}")
+        return jid, model, g, iters, batch, clip, drop, adrop, odt
 
     def status(self) -> dict:
         s = self.sched
@@ -647,7 +651,7 @@ class Controller:
                 act = {"op": "start", "job": j.job_id, "ranks": ranks, "model": rj.model,
                        "iters": max(0, rj.iterations - self.done_iters[j.job_id]),
                        "batch": rj.batch, "grad_clip": rj.grad_clip, "dropout": rj.dropout,
-                       "attn_dropout": rj.attn_dropout,
+                       "attn_dropout": rj.attn_dropout, "opt_dtype": rj.opt_dtype,
                        "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
@@ -858,7 +862,7 @@ class Worker:
         self.hbm_budget = hbm_budget_gb * 2 ** 30 if hbm_budget_gb else None
         self._last_run: Dict[str, int] = {}
         self._round = 0
-        self._need: Dict[str, float] = {}          # model -> measured HBM need of a new job
+        self._need: Dict[object, float] = {}       # model (or (model, "bf16")) -> measured HBM need of a new job
         self._ckpt: Dict[str, dict] = {}           # job -> bytes / seconds since the last report
         self.pressure_spills = 0
         self.pool_evictions = 0
@@ -884,10 +888,19 @@ class Worker:
             return None
         return self.groups[tuple(ranks)]
 
+    @staticmethod
+    def _pool_key(act) -> tuple:
+        """Warm-pool key of a start action: what fixes a trainer's buffers.
+        The optimizer-state format does (bf16 state buffers cannot serve a
+        fp32-state job, nor the reverse), so a bf16-state job's key carries it;
+        the per-job setters (clip, dropouts) are not part of the key."""
+        key = (act["model"], act.get("batch"), tuple(act["ranks"]))
+        return key + ("bf16",) if act.get("opt_dtype") == "bf16" else key
+
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
         data_seed = act["seed"] * 1000 + ranks.index(self.rank)
-        key = (act["model"], act.get("batch"), ranks)
+        key = self._pool_key(act)
         # hipGraph capture (+ instantiation, + a private memory pool per
         # graph) costs tens of ms per fresh trainer. It pays when the
         # trainer outlives the job in the warm pool (later jobs of the shape
@@ -898,6 +911,12 @@ class Worker:
         want = self.use_graph and len(ranks) == 1 and (long_job or self.pool_cap > 0)
         free = self.pool.get(key)
         if free:
+            # the key carries the state format; a pooled trainer of the other
+            # format under it would run the wrong kernels silently
+            want_dt = "bf16" if act.get("opt_dtype") == "bf16" else "fp32"
+            if free[-1].opt_dtype != want_dt:
+                raise RuntimeError(f"warm pool {key}: a {free[-1].opt_dtype}-state trainer is pooled under the "
+                                   f"key of a {want_dt}-state job")
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
@@ -910,7 +929,7 @@ class Worker:
         t = Trainer(act["model"], self.device, batch=act.get("batch"), group=self._group(ranks),
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
                     ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
-                    attn_dropout=act.get("attn_dropout"))
+                    attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"))
         t.pool_key = key
         return t
 
@@ -1022,16 +1041,18 @@ class Worker:
                 n += t.hbm_bytes()
         return n
 
-    def _job_need(self, model: str, batch) -> float:
+    def _job_need(self, model: str, batch, opt_dtype: Optional[str] = None) -> float:
         """HBM a new job of ``model`` needs, in the units the budget counts
         (Trainer.hbm_bytes: state + batch): the measured growth when one was
-        last created here, else 1.5x its optimizer-inclusive state."""
-        if model in self._need:
-            return self._need[model]
+        last created here with the same optimizer-state format, else 1.5x its
+        optimizer-inclusive state (bf16 moments priced at 2 B each)."""
+        nk = (model, "bf16") if opt_dtype == "bf16" else model
+        if nk in self._need:
+            return self._need[nk]
         from ..profiler.skew import model_profile
 
         try:
-            st = model_profile(model).state_bytes("adam")
+            st = model_profile(model).state_bytes("adam", opt_dtype)
         except KeyError:
             st = 1 << 30
         return 1.5 * st
@@ -1107,10 +1128,9 @@ class Worker:
                     continue
                 t = self.trainers.get(a["job"])
                 if t is None:
-                    key = (a["model"], a.get("batch"), tuple(a["ranks"]))
-                    if self.pool.get(key):
+                    if self.pool.get(self._pool_key(a)):
                         continue               # a warm-pool reuse needs no new HBM
-                    self._make_room(self._job_need(a["model"], a.get("batch")), protect, ro)
+                    self._make_room(self._job_need(a["model"], a.get("batch"), a.get("opt_dtype")), protect, ro)
                 elif getattr(t, "_spilled", None):
                     self._make_room(t.hbm_bytes(), protect, ro)
             ta = self._ap("pressure_room", ta)
@@ -1206,7 +1226,8 @@ class Worker:
                         grown = torch.cuda.memory_allocated(self.device) - before
                         if grown > 0:      # a newly built trainer (not a warm-pool reuse)
                             # what _resident_bytes will count for it (state + batch)
-                            self._need[a["model"]] = max(self._need.get(a["model"], 0.0), float(grown))
+                            nk = (a["model"], "bf16") if a.get("opt_dtype") == "bf16" else a["model"]
+                            self._need[nk] = max(self._need.get(nk, 0.0), float(grown))
             elif src == "resident":
                 t = self.trainers.get(a["job"])
                 if t is not None and getattr(t, "_spilled", None):
@@ -1245,7 +1266,8 @@ class Worker:
                 if self.rank in ranks and self.rank in old:
                     t = self.trainers[a["job"]]
                     t.rebind(self._group(ranks))
-                    t.pool_key = (a["model"], a.get("batch"), ranks)
+                    # (the trainer's own state format, whatever the action carries)
+                    t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype))
                 elif self.rank in ranks:
                     self._bind(self.trainers[a["job"]], ranks)
                 if self.rank in ranks and "step" in a:

@@ -53,7 +53,7 @@ class VirtualClock:
         self.t += s
 
 
-def _state_bytes(model: str) -> float:
+def _state_bytes(model: str, opt_dtype: Optional[str] = None) -> float:
     from ..models import MODELS
 
     try:
@@ -61,7 +61,7 @@ def _state_bytes(model: str) -> float:
     except KeyError:
         return 0.0
     opt = MODELS[model].opt if model in MODELS else "sgd"
-    return float(prof.state_bytes(opt))
+    return float(prof.state_bytes(opt, opt_dtype))    # (bf16-state jobs: 2 B per moment)
 
 
 class FakeCluster:
@@ -84,6 +84,7 @@ class FakeCluster:
         self.held: Dict[str, Tuple[int, ...]] = {}      # job -> ranks holding its state in HBM
         self.spilled: Set[str] = set()
         self.model: Dict[str, str] = {}
+        self.odt: Dict[str, Optional[str]] = {}      # job -> optimizer-state format (start action's opt_dtype)
         self.groups: Set[Tuple[int, ...]] = set()
         self.stats = {"p2p_bytes": 0.0, "spill_bytes": 0.0, "restore_bytes": 0.0, "starts": 0,
                       "resident_resumes": 0, "rounds": 0}
@@ -154,25 +155,27 @@ class FakeCluster:
                 if job in self.spilled:
                     raise ProtocolError(f"consolidate of {job} after its spill")
                 w = len(ranks)
-                b = _state_bytes(self.model[job]) * (w - 1) / w
+                b = _state_bytes(self.model[job], self.odt.get(job)) * (w - 1) / w
                 charge(ranks, b / self.xgmi)
                 self.stats["consolidate_bytes"] = self.stats.get("consolidate_bytes", 0.0) + b * w
             elif op == "spill":
                 if job not in self.held or job in self.spilled:
                     raise ProtocolError(f"spill of job {job} that is not resident")
-                b = _state_bytes(self.model[job])
+                b = _state_bytes(self.model[job], self.odt.get(job))
                 charge(self.held[job], b / self.host)
                 self.stats["spill_bytes"] += b * len(self.held[job])
                 self.spilled.add(job)
             elif op == "start":
-                # (the per-job recipe keys, grad_clip / dropout / attn_dropout,
-                # change no cost in the world model: accepted and ignored)
+                # (the per-job recipe keys grad_clip / dropout / attn_dropout
+                # change no cost in the world model: accepted and ignored;
+                # opt_dtype sizes the state that spills and moves)
                 ranks = tuple(a["ranks"])
                 if len(ranks) > 1 and ranks not in self.groups:
                     raise ProtocolError(f"gang {job} started on {ranks} without a communicator")
                 self.model[job] = a["model"]
+                self.odt[job] = a.get("opt_dtype")
                 src = a["source"]
-                b = _state_bytes(a["model"])
+                b = _state_bytes(a["model"], a.get("opt_dtype"))
                 if src == "fresh":
                     if job in self.held:
                         raise ProtocolError(f"fresh start of {job} whose state is still held")

@@ -28,9 +28,21 @@ class Trainer:
                  model_kwargs: Optional[dict] = None, lr: Optional[float] = None,
                  overlap_wgrad: Optional[bool] = None, branches: Optional[bool] = None,
                  ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
-                 dropout: Optional[float] = None, attn_dropout: Optional[float] = None):
+                 dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
+                 opt_dtype: Optional[str] = None):
         self.model_name = model
         self.spec = MODELS[model]
+        if opt_dtype is None:
+            opt_dtype = self.spec.opt_dtype
+        if opt_dtype not in (None, "fp32", "bf16"):
+            raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', got {opt_dtype!r}")
+        # format of the optimizer state (README "bf16 optimizer state"). It
+        # fixes the buffer types, so it is set at construction (and is part of
+        # the worker's warm-pool key), not by a per-job setter
+        self.opt_dtype = "bf16" if opt_dtype == "bf16" else "fp32"
+        if self.opt_dtype == "bf16" and ddp_shard and group is not None and comm_size(group) > 1:
+            raise ValueError("opt_dtype='bf16' with ddp_shard is not supported: the sharded gang's slice "
+                             "launches and state all-gather are fp32-state only")
         if dropout is None:
             dropout = self.spec.dropout
         if attn_dropout is None:
@@ -51,11 +63,8 @@ class Trainer:
         n = self.arena.numel
         self.opt = self.spec.opt
         self.lr = lr if lr is not None else self.spec.lr
-        if self.opt == "sgd":
-            self.opt_state = [torch.zeros(n, dtype=torch.float32, device=self.device)]
-        else:
-            self.opt_state = [torch.zeros(n, dtype=torch.float32, device=self.device),
-                              torch.zeros(n, dtype=torch.float32, device=self.device)]
+        sdt = torch.bfloat16 if self.opt_dtype == "bf16" else torch.float32
+        self.opt_state = [torch.zeros(n, dtype=sdt, device=self.device) for _ in range(1 if self.opt == "sgd" else 2)]
         self.step_count = 0
         self.data = synthetic_batch(model, self.batch, self.device,
                                     seed=seed if data_seed is None else data_seed)
@@ -327,7 +336,18 @@ class Trainer:
             guard = self.model.err if self.uses_persist else None
             zf = A.n_store if Fx.STORE_GRAD else 0
             clip = self._clip_launch(gscale)
-            if self.opt == "sgd":
+            if self.opt_dtype == "bf16":
+                # bf16 moments, stochastically rounded: the draws are a pure
+                # function of (seed, step, arena index), nothing is stored
+                seed = int(self.seed) & 0xFFFFFFFF
+                if self.opt == "sgd":
+                    T.sgd_step_bf16s(A.master, A.grad, self.opt_state[0], A.shadow, self.lr, 0.9, self.spec.wd,
+                                     gscale, False, True, seed, self.step_count, 0, guard, zf, A.n_decay, clip)
+                else:
+                    T.adam_step_bf16s(A.master, A.grad, self.opt_state[0], self.opt_state[1], A.shadow, self.lr,
+                                      0.9, 0.98, 1e-9, self.spec.wd, self.step_count, gscale, True, seed, 0,
+                                      guard, zf, A.n_decay, clip)
+            elif self.opt == "sgd":
                 T.sgd_step(A.master, A.grad, self.opt_state[0], A.shadow, self.lr, 0.9, self.spec.wd, gscale, False,
                            True, guard, zf, A.n_decay, clip)
             else:
@@ -367,14 +387,26 @@ class Trainer:
                 # GNMT: a step whose persistent recurrence timed out (this
                 # job's own timeout word) only resets the gradient
                 guard = self.model.err if self.uses_persist else None
-                if self.opt == "sgd":
+                if self.opt_dtype == "bf16":
+                    # base = lo: a region draws what a launch over the whole
+                    # arena draws for the same elements
+                    seed = int(self.seed) & 0xFFFFFFFF
+                    if self.opt == "sgd":
+                        T.sgd_step_bf16s(w, g, self.opt_state[0][lo:hi], wb, self.lr, 0.9, wd, gscale, False, zero,
+                                         seed, self.step_count, lo, guard, 0, -1, clip)
+                    else:
+                        T.adam_step_bf16s(w, g, self.opt_state[0][lo:hi], self.opt_state[1][lo:hi], wb, self.lr,
+                                          0.9, 0.98, 1e-9, wd, self.step_count, gscale, zero, seed, lo, guard,
+                                          0, -1, clip)
+                elif self.opt == "sgd":
                     T.sgd_step(w, g, self.opt_state[0][lo:hi], wb, self.lr, 0.9, wd, gscale, False, zero, guard,
                                0, -1, clip)
                 else:
                     T.adam_step(w, g, self.opt_state[0][lo:hi], self.opt_state[1][lo:hi], wb, self.lr,
                                 0.9, 0.98, 1e-9, wd, self.step_count, gscale, zero, guard, 0, -1, clip)
             else:
-                _cpu_opt(self.opt, w, g, self.opt_state, lo, hi, wb, self.lr, wd, gscale, self.step_count)
+                _cpu_opt(self.opt, w, g, self.opt_state, lo, hi, wb, self.lr, wd, gscale, self.step_count,
+                         seed=self.seed if self.opt_dtype == "bf16" else None)
         if sharded:
             A.grad.zero_()                 # the slices of the other members held local partials
             self.ddp.gather_shadow()
@@ -597,7 +629,7 @@ class Trainer:
         for b, n in ((A.master, A.numel * 4), (A.shadow, A.numel * 2), (A.grad, A.numel * 4)):
             b.untyped_storage().resize_(n)
         for t in self.opt_state:
-            t.untyped_storage().resize_(t.numel() * 4)
+            t.untyped_storage().resize_(t.numel() * t.element_size())
         nbytes = 0
         for b, h, _ in handles:
             self._engine.restore(h, b)
@@ -683,6 +715,8 @@ class Trainer:
         different GPUs): new communicator, fresh bucketer."""
         if self.grad_clip is not None and self.ddp_shard and group is not None and comm_size(group) > 1:
             raise ValueError("grad_clip with ddp_shard is not supported")
+        if self.opt_dtype == "bf16" and self.ddp_shard and group is not None and comm_size(group) > 1:
+            raise ValueError("opt_dtype='bf16' with ddp_shard is not supported")
         # sharded state survives only a re-created communicator over the SAME
         # rank set (same member positions); anything else needs consolidate()
         dirty = self.state_sharded
@@ -719,7 +753,7 @@ class Trainer:
     def hbm_bytes(self) -> int:
         """Device bytes this trainer pins: state buffers + batch (the graph's
         private activation pool is not visible here)."""
-        n = self.arena.numel * (4 + 2 + 4) + sum(t.numel() * 4 for t in self.opt_state)
+        n = self.arena.numel * (4 + 2 + 4) + sum(t.numel() * t.element_size() for t in self.opt_state)
         n += sum(v.numel() * v.element_size() for v in self.data.values())
         return n
 
@@ -738,19 +772,34 @@ class Trainer:
         self.arena.on_grad_ready = None
 
 
-def _cpu_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step):
+def _cpu_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, seed=None):
+    """The optimizer step in plain torch. ``seed`` not None: the state is
+    bf16 -- widened, updated in fp32 (the weights come from the unrounded
+    moments, as in the kernels) and stored back with the stochastic rounding
+    of the device path (Fx.opt_state_draws / Fx.sr_bf16, arena elements
+    lo .. hi)."""
     gg = g * gscale
+    sr = seed is not None
+    if sr:
+        um, uv = Fx.opt_state_draws(lo, hi - lo, seed, step)
     if opt == "sgd":
-        m = state[0][lo:hi]
+        m = state[0][lo:hi].float() if sr else state[0][lo:hi]
         d = gg + wd * w
         m.mul_(0.9).add_(d)
         w.sub_(lr * m)
+        if sr:
+            state[0][lo:hi] = Fx.sr_bf16(m, um)
     else:
         m, v = state[0][lo:hi], state[1][lo:hi]
+        if sr:
+            m, v = m.float(), v.float()
         m.mul_(0.9).add_(0.1 * gg)
         v.mul_(0.98).add_(0.02 * gg * gg)
         mh = m / (1 - 0.9 ** step)
         vh = v / (1 - 0.98 ** step)
         w.sub_(lr * (mh / (vh.sqrt() + 1e-9) + wd * w))
+        if sr:
+            state[0][lo:hi] = Fx.sr_bf16(m, um)
+            state[1][lo:hi] = Fx.sr_bf16(v, uv)
     g.zero_()
     wb.copy_(w.to(torch.bfloat16))

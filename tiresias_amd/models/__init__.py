@@ -52,6 +52,10 @@ class ModelSpec:
     # attention-probability dropout of the job's recipe (Trainer.set_attn_dropout,
     # --attn-dropout); None = off. Models without the attribute ignore it
     attn_dropout: Optional[float] = None
+    # format of the optimizer state (Trainer opt_dtype, --opt-dtype): None /
+    # "fp32" keep fp32 moments, "bf16" keeps them in bf16 with stochastic
+    # rounding. No shipped model sets it
+    opt_dtype: Optional[str] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

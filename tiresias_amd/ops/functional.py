@@ -860,6 +860,40 @@ def attn_dropout_mask(B: int, H: int, Sq: int, Sk: int, site: int, seed: int, st
     return (u.reshape(B, H, 4 * nq, 4 * nk)[:, :, :Sq, :Sk] >= thr).contiguous()
 
 
+# bf16 optimizer state (Trainer opt_dtype="bf16"; csrc/include/tam/philox.h
+# "Optimizer-state rounding contract"): moments are stored in bf16 with
+# stochastic rounding. One Philox call covers 4 consecutive arena elements:
+# for arena element e, q = e >> 2 and j = e & 3, the counter is (q &
+# 0xffffffff, q >> 32, 0x40000000, step), the key (seed, 0); u_m = out[j] &
+# 0xffff rounds the first moment / SGD momentum, u_v = out[j] >> 16 Adam's
+# second moment. step is the 1-based optimizer step. The key holds no gang
+# position, so the members of a non-sharded gang store identical state.
+OPT_STATE_SITE = 0x40000000
+
+
+def opt_state_draws(base: int, n: int, seed: int, step: int):
+    """The 16-bit draws (u_m, u_v), int64 [n] on the CPU, of arena elements
+    base .. base + n."""
+    q0 = base >> 2
+    q = torch.arange(q0, (base + n + 3) >> 2, dtype=torch.int64)
+    o = philox4x32_10(q & _M32, q >> 32, torch.full_like(q, OPT_STATE_SITE), torch.full_like(q, step & _M32),
+                      seed & _M32, 0)
+    w = torch.stack(o, 1).reshape(-1)[base - 4 * q0: base - 4 * q0 + n]
+    return w & 0xFFFF, (w >> 16) & 0xFFFF
+
+
+def sr_bf16(x: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """fp32 ``x`` -> bf16, stochastically rounded with the 16-bit draws ``u``
+    (int64, x's shape): (bits + u) >> 16 for finite values -- the magnitude
+    goes up with probability (bits & 0xffff) / 65536, a carry into the
+    exponent included -- inf passes through, NaN stays NaN (quiet bit set)."""
+    b = x.contiguous().view(torch.int32).to(torch.int64) & _M32
+    special = (b & 0x7F800000) == 0x7F800000
+    quiet = ((b & 0x007FFFFF) != 0).to(torch.int64) * 0x40
+    r = torch.where(special, (b >> 16) | quiet, (b + u.to(b.device)) >> 16)
+    return ((r ^ 0x8000) - 0x8000).to(torch.int16).view(torch.bfloat16)
+
+
 _DROP_REC: Optional[torch.Tensor] = None
 _DROP_SITE = 0
 _ATTN_DROP_SITE = 0

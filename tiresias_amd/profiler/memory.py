@@ -41,7 +41,8 @@ def estimate_gpu_memory(model: str, batch: int = 32, capacity_mb: float = 288 * 
     return {"weights_mb": w, "total_mb": total, "fraction": min(1.0, total / capacity_mb)}
 
 
-def measure(model: str, batch: Optional[int] = None, steps: int = 3) -> Dict[str, float]:
+def measure(model: str, batch: Optional[int] = None, steps: int = 3,
+            opt_dtype: Optional[str] = None) -> Dict[str, float]:
     import torch
 
     from ..executor.trainer import Trainer
@@ -49,7 +50,7 @@ def measure(model: str, batch: Optional[int] = None, steps: int = 3) -> Dict[str
     dev = torch.device("cuda", torch.cuda.current_device())
     torch.cuda.reset_peak_memory_stats(dev)
     base = torch.cuda.memory_allocated(dev)
-    t = Trainer(model, dev, batch=batch)
+    t = Trainer(model, dev, batch=batch, opt_dtype=opt_dtype)
     t.step()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()

@@ -43,9 +43,11 @@ class ModelProfile:
     def skew(self) -> float:
         return self.largest_mb / self.total_mb if self.total_mb > 0 else 0.0
 
-    def state_bytes(self, opt: str = "sgd") -> int:
-        # master fp32 + bf16 shadow + optimizer state (1 or 2 fp32 buffers)
-        return self.params * (4 + 2 + (4 if opt == "sgd" else 8))
+    def state_bytes(self, opt: str = "sgd", opt_dtype: Optional[str] = None) -> int:
+        # master fp32 + bf16 shadow + optimizer state (1 or 2 buffers, fp32
+        # or, for a job with opt_dtype="bf16", bf16)
+        per = 2 if opt_dtype == "bf16" else 4
+        return self.params * (4 + 2 + (1 if opt == "sgd" else 2) * per)
 
 
 class _ShapeArena:

@@ -5,7 +5,12 @@ master+grad+state reads, master+state+grad-zero+bf16 shadow writes).
 ``--clip`` also times, per arena at the production variant / grid, the
 global-norm pass alone (grad_sumsq + grad_clip_finalize, 4 B/param read) and
 the optimizer step with and without the norm pass + ``clip`` record in front
-of it (the difference is what clipping adds to a step)."""
+of it (the difference is what clipping adds to a step).
+
+``--bf16-state`` also times, per arena at the production variant / grid, the
+step with fp32 state against the step with bf16 state and Philox stochastic
+rounding (``*_step_bf16s``), interleaved, with the bytes each form moves per
+element (Adam 34 -> 26, SGD 26 -> 22)."""
 import json
 import os
 import sys
@@ -32,6 +37,9 @@ def main():
     clip_rows = "--clip" in sys.argv
     if clip_rows:
         sys.argv.remove("--clip")
+    bf16_rows = "--bf16-state" in sys.argv
+    if bf16_rows:
+        sys.argv.remove("--bf16-state")
     _lib.load(required=True)
     T = _lib.ops()
     dev = torch.device("cuda", 0)
@@ -85,6 +93,33 @@ def main():
                     print(json.dumps(r), flush=True)
                     out.append(r)
             del part, rec
+        if bf16_rows:
+            mb = torch.zeros(n, device=dev, dtype=torch.bfloat16)
+            vb = torch.zeros(n, device=dev, dtype=torch.bfloat16) if opt == "adam" else None
+            step_no = [0]
+
+            def f32():
+                if opt == "sgd":
+                    T.sgd_step(w, g, m, wb, 0.1, 0.9, 1e-4, 1.0, False, True)
+                else:
+                    T.adam_step(w, g, m, v, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, 3, 1.0, True)
+
+            def b16():
+                step_no[0] += 1
+                if opt == "sgd":
+                    T.sgd_step_bf16s(w, g, mb, wb, 0.1, 0.9, 1e-4, 1.0, False, True, 1, step_no[0], 0)
+                else:
+                    T.adam_step_bf16s(w, g, mb, vb, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, step_no[0], 1.0, True, 1, 0)
+
+            per = {"sgd": (26, 22), "adam": (34, 26)}[opt]
+            for _ in range(3):                                                # three interleaved rounds
+                for kind, fn, bpe in (("fp32_state", f32, per[0]), ("bf16_state", b16, per[1])):
+                    us = timeit(fn)
+                    r = dict(model=name, opt=opt, kind=kind, params=n, bytes_per_elem=bpe, us=round(us, 1),
+                             tb_per_s=round(bpe * n / us / 1e6, 2))
+                    print(json.dumps(r), flush=True)
+                    out.append(r)
+            del mb, vb
         del v
         del w, g, m, wb
         torch.cuda.empty_cache()
