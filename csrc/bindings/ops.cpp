@@ -441,6 +441,13 @@ std::string gemm_routes_op() {
     if (pc != g_p8_cfg.end()) o << " " << pc->second.first << " " << pc->second.second;
     o << "\n";
   }
+  // pointwise-conv routes (tune_conv_pw): layout "PW", the mode column holds
+  // the epilogue kind, the dma / p8 columns the conv core's / best tile's ms
+  std::vector<tam::ConvPwRoute> pw(tam::conv_pw_routes(nullptr, 0));
+  pw.resize(tam::conv_pw_routes(pw.data(), (int)pw.size()));
+  for (const auto& r : pw)
+    o << r.M << " " << r.N << " " << r.K << " PW " << r.kind << " 0 " << (r.kind != 0) << " "
+      << (r.tile > 0 ? "p8" : "dma") << " 1e+30 1e+30 " << r.ms_conv << " " << r.ms_p8 << " " << r.tile << " 1\n";
   return o.str();
 }
 
@@ -462,6 +469,16 @@ int64_t gemm_routes_load_op(const std::string& text) {
     std::array<float, 4> t{};
     if (!(ls >> M >> N >> K >> lay >> mode >> f32 >> epi >> rt >> t[0] >> t[1] >> t[2] >> t[3])) continue;
     if (lay.size() != 2 || M <= 0 || N <= 0 || K <= 0) continue;
+    if (lay == "PW") {
+      int tile = 0, sp = 0;
+      ls >> tile >> sp;
+      const bool p8 = rt == "p8";
+      if ((!p8 && rt != "dma") || mode < 0 || mode > 4) continue;
+      if (p8 && !(tile == 64 || tile == 65 || tile == 128 || tile == 129 || tile == 256)) continue;
+      tam::conv_pw_route_set({(int)M, (int)N, (int)K, (int)mode, p8 ? tile : 0, t[2], t[3]}, true);
+      ++n;
+      continue;
+    }
     const int route = rt == "lib" ? 1 : rt == "dma" ? 2 : rt == "p8" ? 3 : rt == "mfma" ? 0 : -1;
     if (route < 0) continue;
     const GemmKey key{M, N, K, lay[0] == 'K', lay[1] == 'K', mode, (bool)f32, (bool)epi};
@@ -499,6 +516,55 @@ tam::ConvGeom geom(const Tensor& x, const Tensor& w, const Tensor& y, int64_t st
   return g;
 }
 
+// Measured route of a pointwise conv the gemm8p core accepts
+// (tam::conv_pw_gemm_kind): the conv core (with whatever split + reduce it
+// chooses) against every eligible gemm8p tile, each timed like a plain GEMM's
+// candidates -- HIP events, scratch output and statistics, outside graph
+// capture, two interleaved rounds -- and cached per (M, N, K, epilogue kind).
+// a / b: x, w (forward) or dy, wt (dgrad; w: the weight as stored).
+void tune_conv_pw(bool dgrad, const Tensor& a, const Tensor& b, const tam::ConvGeom& g, const tam::Epi& ep,
+                  const Tensor* w = nullptr) {
+  if (tam::conv_pw_gemm_mode() != 1 || g.R != 1 || g.S != 1 || g.stride != 1 || g.pad != 0) return;
+  const int M = g.N * g.H * g.W, N = dgrad ? g.C : g.K, K = dgrad ? g.K : g.C;
+  const int kind = tam::conv_pw_gemm_kind(M, N, K, ep);
+  if (kind < 0 || tam::conv_pw_route_get(M, N, K, kind) >= 0) return;
+  hipStream_t s = cur_stream(a);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TAM_HIP_CHECK(hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone) return;   // never tune in a graph: the conv core runs
+  Tensor scratch = at::empty({M, N}, a.options());
+  Tensor sstats;
+  tam::Epi es = ep;
+  es.c = scratch.data_ptr();
+  es.ldc = N;
+  if (ep.stats) {
+    sstats = at::zeros({tam::BN_SHARDS * 2 * N}, a.options().dtype(at::kDouble));
+    es.stats = sstats.data_ptr<double>();
+  }
+  const long wsf = dgrad ? tam::conv_dgrad_split_ws(g) : tam::conv_fwd_split_ws(g);
+  Tensor ws;
+  if (wsf > 0) ws = at::empty({wsf}, a.options().dtype(at::kFloat));
+  float* wsp = wsf > 0 ? ws.data_ptr<float>() : nullptr;
+  auto run = [&](int tile) {
+    if (dgrad) tam::conv_dgrad(bp(a), bp(*w), bp(b), g, es, s, wsp, wsf, tile);
+    else tam::conv_fwd(bp(a), bp(b), g, es, s, wsp, wsf, tile);
+  };
+  std::vector<int> cands{64, 128};
+  if ((K / 64) % 2 == 0) { cands.push_back(65); cands.push_back(129); }
+  if (M >= 256 && N >= 256) cands.push_back(256);
+  float t_conv = 1e30f, t_p8 = 1e30f;
+  int best = 0;
+  for (int round = 0; round < 2; ++round) {
+    t_conv = std::min(t_conv, time_ms(s, [&] { run(0); }));
+    for (int tile : cands) {
+      const float ms = time_ms(s, [&] { run(tile); });
+      if (ms < t_p8) { t_p8 = ms; best = tile; }
+    }
+  }
+  // as for plain GEMMs: another path only where it timed > 5 % faster
+  tam::conv_pw_route_set({M, N, K, kind, t_p8 < 0.95f * t_conv ? best : 0, t_conv, t_p8}, false);
+}
+
 // stats (optional, fp64 [2K], zeroed by the caller): BatchNorm sums of y
 // accumulated by the conv epilogue; returns 1 when they were (0: this path
 // computes none, the BN reduces y itself)
@@ -517,7 +583,8 @@ int64_t conv_fwd_op(const Tensor& x, const Tensor& w, const Tensor& y, int64_t s
                 "tam.conv_fwd: stats must be a contiguous fp64 [BN_SHARDS * 2K] tensor");
     ep.stats = stats->data_ptr<double>();
   }
-  const long wsf = tam::conv_fwd_split_ws(g);
+  tune_conv_pw(false, x, w, g, ep);
+  const long wsf = tam::conv_fwd_split_ws(g, &ep);
   Tensor ws;
   if (wsf > 0) ws = at::empty({wsf}, x.options().dtype(at::kFloat));
   return tam::conv_fwd(bp(x), bp(w), g, ep, cur_stream(x), wsf > 0 ? ws.data_ptr<float>() : nullptr, wsf);
@@ -540,7 +607,8 @@ void conv_dgrad_op(const Tensor& dy, const Tensor& w, const Tensor& wt, const Te
     TORCH_CHECK(mask->numel() == dx.numel(), "tam.conv_dgrad: mask size");
     ep.mask = bp(*mask); ep.ldm = g.C;
   }
-  const long wsf = tam::conv_dgrad_split_ws(g);
+  tune_conv_pw(true, dy, wt, g, ep, &w);
+  const long wsf = tam::conv_dgrad_split_ws(g, &ep);
   Tensor ws;
   if (wsf > 0) ws = at::empty({wsf}, dy.options().dtype(at::kFloat));
   tam::conv_dgrad(bp(dy), bp(w), bp(wt), g, ep, cur_stream(dy), wsf > 0 ? ws.data_ptr<float>() : nullptr, wsf);
@@ -643,7 +711,8 @@ int64_t conv_dgrad_pre_op(const Tensor& dy, const Tensor& w, const Tensor& wt, c
     ep.bnmean = bnmean->data_ptr<float>();
     ep.bnrstd = bnrstd->data_ptr<float>();
   }
-  const long wsf = ep.bnx ? 0 : tam::conv_dgrad_split_ws(g);
+  tune_conv_pw(true, dy, wt, g, ep, &w);
+  const long wsf = ep.bnx ? 0 : tam::conv_dgrad_split_ws(g, &ep);
   Tensor ws;
   if (wsf > 0) ws = at::empty({wsf}, dy.options().dtype(at::kFloat));
   return tam::conv_dgrad(bp(dy), bp(w), bp(wt), g, ep, cur_stream(dy), wsf > 0 ? ws.data_ptr<float>() : nullptr,
@@ -1057,6 +1126,7 @@ void gemm_dma_policy_op(int64_t p, int64_t cfg) {
 
 void gemm8p_policy_op(int64_t mode, int64_t tile) { tam::gemm8p_policy((int)mode, (int)tile); }
 void gemm_pw_policy_op(int64_t on) { tam::gemm_pw_policy((int)on); }
+void conv_pw_gemm_policy_op(int64_t mode, int64_t tile) { tam::conv_pw_gemm_policy((int)mode, (int)tile); }
 
 // every registered tuning knob (common.h TAM_KNOB): names (comma-joined, in
 // registration order), current values, and a bulk restore
@@ -1498,6 +1568,7 @@ TORCH_LIBRARY(tam, m) {
   m.def("gemm_force(int cfg, int splits) -> ()", &gemm_force_op);
   m.def("gemm8p_policy(int mode, int tile) -> ()", &gemm8p_policy_op);
   m.def("gemm_pw_policy(int on) -> ()", &gemm_pw_policy_op);
+  m.def("conv_pw_gemm_policy(int mode, int tile) -> ()", &conv_pw_gemm_policy_op);
   m.def("policy_names() -> str", &policy_names_op);
   m.def("policy_state() -> int[]", &policy_state_op);
   m.def("policy_load(int[] v) -> ()", &policy_load_op);

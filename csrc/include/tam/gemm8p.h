@@ -172,10 +172,15 @@ __device__ __forceinline__ void p8_mfma(f32x4_t (&acc)[TI][TJ], const s16x8_t (&
 // grid, staged through the block's LDS (smem, >= NW * 32 * (WTN + 4) * 4 B).
 // J0 / NJ: only fragment columns [J0, J0 + NJ) of every wave tile (the two K
 // groups of gemm8p_ks2_kernel store one half each)
-template <int BM, int BN, int WNW, int TI, int TJ, int J0 = 0, int NJ = TJ>
+// STATS (bf16 16-B store path only; the launcher checks its conditions): st[0..7]
+// += this lane's column sums of the stored (bf16-rounded) values of rows < M,
+// st[8..15] += their squares -- every 16-B chunk a lane stores is chunk
+// lane % CPR of its row, so a lane owns the same 8 columns throughout
+// (p8_stats_flush reduces them)
+template <int BM, int BN, int WNW, int TI, int TJ, int J0 = 0, int NJ = TJ, bool STATS = false>
 __device__ __forceinline__ void p8_epilogue(const P8Args& a, const Epi& ep, f32x4_t (&acc)[TI][TJ], char* smem,
                                             const int m0, const int n0, const int kz, const int wid,
-                                            const int lane) {
+                                            const int lane, float* st = nullptr) {
   using G = P8Geo<BM, BN, WNW>;
   const int wm = wid / WNW, wn = wid % WNW;
 
@@ -195,6 +200,7 @@ __device__ __forceinline__ void p8_epilogue(const P8Args& a, const Epi& ep, f32x
   const bool mask16 = ep.mask == nullptr || ((ep.ldm & 7) == 0 && (((uintptr_t)ep.mask) & 15) == 0);
   if (!ep.c_f32 && mask16 && (ep.ldc & 7) == 0 && (((uintptr_t)ep.c) & 15) == 0) {
     constexpr int LDW = WTN + 8, CPR = WTN / 8;
+    static_assert(!STATS || 64 % CPR == 0, "a lane keeps one chunk column");
     bf16_t* slab = (bf16_t*)(smem + wid * (32 * LDW * 2));
 #pragma unroll
     for (int h = 0; h < TI / 2; ++h) {
@@ -242,6 +248,15 @@ __device__ __forceinline__ void p8_epilogue(const P8Args& a, const Epi& ep, f32x
                                bf2f((bf16_t)(vw[e] >> 16)) + bf2f((bf16_t)(ow[e] >> 16)));
           }
           *(uint4*)dst = v;
+          if constexpr (STATS) {
+            const uint32_t* vw = (const uint32_t*)&v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float lo = __uint_as_float(vw[e] << 16), hi = __uint_as_float(vw[e] & 0xffff0000u);
+              st[2 * e] += lo; st[8 + 2 * e] += lo * lo;
+              st[2 * e + 1] += hi; st[8 + 2 * e + 1] += hi * hi;
+            }
+          }
         } else {
           for (int e = 0; e < 8 && col + e < a.N; ++e) {
             float v = bf2f(src[e]);
@@ -328,6 +343,48 @@ __device__ __forceinline__ void p8_epilogue(const P8Args& a, const Epi& ep, f32x
   }
 }
 
+// BatchNorm statistics of the tile a STATS epilogue stored (Epi::stats, fp64
+// [BN_SHARDS][2N] sum | sum of squares): the lanes of a wave that share a
+// chunk column are summed by shuffles, the tile's two M waves through LDS
+// (red: 2 * NW * 16 NJ floats the epilogue slabs do not touch), then ONE fp64
+// atomic per column per tile into shard (M-tile % BN_SHARDS). Called by every
+// thread of the block (one __syncthreads). j0 / NJ: the fragment columns the
+// epilogue stored.
+template <int BM, int BN, int WNW, int NJ>
+__device__ __forceinline__ void p8_stats_flush(const P8Args& a, const Epi& ep, float (&st)[16], float* red,
+                                               const int m0, const int n0, const int j0, const int wid,
+                                               const int lane) {
+  using G = P8Geo<BM, BN, WNW>;
+  constexpr int WC = 16 * NJ, CPR = WC / 8;
+#pragma unroll
+  for (int o = CPR; o < 64; o <<= 1)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] += __shfl_xor(st[e], o, 64);
+  if (lane < CPR) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      red[wid * 2 * WC + lane * 8 + e] = st[e];
+      red[wid * 2 * WC + WC + lane * 8 + e] = st[8 + e];
+    }
+  }
+  __syncthreads();
+  if (wid < WNW) {   // the wm = 0 wave of each column strip adds its wm = 1 partner
+    double* sh = ep.stats + (long)((m0 / BM) % BN_SHARDS) * 2 * a.N;
+    for (int e = lane; e < 2 * WC; e += 64) {
+      const int col = n0 + wid * G::WTN + 16 * j0 + e % WC;
+      if (col < a.N)
+        unsafeAtomicAdd(sh + (e >= WC ? a.N : 0) + col, (double)(red[wid * 2 * WC + e] + red[(wid + WNW) * 2 * WC + e]));
+    }
+  }
+}
+// byte offset of p8_stats_flush's scratch in a tile's LDS: past the epilogue slabs
+template <int BM, int BN, int WNW>
+constexpr int p8_stats_off() {
+  using G = P8Geo<BM, BN, WNW>;
+  static_assert(G::NW * 32 * (G::WTN + 4) * 4 + G::NW * 2 * G::WTN * 4 <= G::LDS, "stats scratch fits the tile's LDS");
+  return G::NW * 32 * (G::WTN + 4) * 4;
+}
+
 // One schedule (measured best of six in round 2, profiles/r2/gemm8p_sched_ab.json;
 // the other five were deleted in round 5): one barrier per phase, B fragments
 // read before A (pinned order), and per-fragment lgkmcnt waits instead of a
@@ -357,7 +414,7 @@ __device__ __forceinline__ void p8_tile_origin(const P8Args& a, const int bid, i
 // then the partial tiles summed through LDS and stored by group 0. For tile
 // grids of one block per CU (the N = 512 projections) it puts two waves on
 // every SIMD without a split-K slab pass.
-template <int BM, int BN, int WNW, bool AK, bool BK, int KS = 1>
+template <int BM, int BN, int WNW, bool AK, bool BK, int KS = 1, bool STATS = false>
 __device__ __forceinline__ void gemm8p_body(const P8Args& a, const Epi& ep, const int bid, const int kz,
                                             const int kt_lo = -1, const int kt_hi = -1) {
   using G = P8Geo<BM, BN, WNW>;
@@ -488,38 +545,54 @@ __device__ __forceinline__ void gemm8p_body(const P8Args& a, const Epi& ep, cons
           else acc[i][JH + j][r] += o;
         }
     __syncthreads();   // partials read before the epilogue slabs reuse the images
-    if (grp == 0) p8_epilogue<BM, BN, WNW, TI, TJ, 0, JH>(a, ep, acc, smem_all, m0, n0, kz, wid, lane);
-    else p8_epilogue<BM, BN, WNW, TI, TJ, JH, JH>(a, ep, acc, smem_all + G::LDS, m0, n0, kz, wid, lane);
+    float st[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] = 0.f;
+    if (grp == 0) p8_epilogue<BM, BN, WNW, TI, TJ, 0, JH, STATS>(a, ep, acc, smem_all, m0, n0, kz, wid, lane, st);
+    else p8_epilogue<BM, BN, WNW, TI, TJ, JH, JH, STATS>(a, ep, acc, smem_all + G::LDS, m0, n0, kz, wid, lane, st);
+    // after the in-block reduction: each group flushes the columns it stored
+    if constexpr (STATS)
+      p8_stats_flush<BM, BN, WNW, JH>(a, ep, st, (float*)(smem_all + grp * G::LDS + p8_stats_off<BM, BN, WNW>()), m0,
+                                      n0, grp * JH, wid, lane);
     return;
   }
-  p8_epilogue<BM, BN, WNW>(a, ep, acc, smem_all, m0, n0, kz, wid, lane);
+  if constexpr (STATS) {
+    float st[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) st[e] = 0.f;
+    p8_epilogue<BM, BN, WNW, TI, TJ, 0, TJ, true>(a, ep, acc, smem_all, m0, n0, kz, wid, lane, st);
+    p8_stats_flush<BM, BN, WNW, TJ>(a, ep, st, (float*)(smem_all + p8_stats_off<BM, BN, WNW>()), m0, n0, 0, wid, lane);
+  } else {
+    p8_epilogue<BM, BN, WNW>(a, ep, acc, smem_all, m0, n0, kz, wid, lane);
+  }
 }
 
 // the in-block two-group K split of gemm8p_body (KS = 2): 2 x the tile's waves
-template <int BM, int BN, int WNW, bool AK, bool BK>
+template <int BM, int BN, int WNW, bool AK, bool BK, bool STATS = false>
 __global__ void __launch_bounds__(2 * 128 * WNW, 1) gemm8p_ks2_kernel(P8Args a, Epi ep) {
-  gemm8p_body<BM, BN, WNW, AK, BK, 2>(a, ep, xcd_remap(blockIdx.x, gridDim.x), blockIdx.z);
+  gemm8p_body<BM, BN, WNW, AK, BK, 2, STATS>(a, ep, xcd_remap(blockIdx.x, gridDim.x), blockIdx.z);
 }
 
-template <int BM, int BN, int WNW, bool AK, bool BK>
+template <int BM, int BN, int WNW, bool AK, bool BK, bool STATS = false>
 void p8_launch_ks2(const P8Args& g, const Epi& ep, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemm8p_ks2_kernel<BM, BN, WNW, AK, BK>), grid, dim3(2 * P8Geo<BM, BN, WNW>::THREADS), 0, s,
-                     g, ep);
+  hipLaunchKernelGGL((gemm8p_ks2_kernel<BM, BN, WNW, AK, BK, STATS>), grid, dim3(2 * P8Geo<BM, BN, WNW>::THREADS), 0,
+                     s, g, ep);
 }
 
-template <int BM, int BN, int WNW, bool AK, bool BK>
+// STATS: the bf16-store epilogue also accumulates Epi::stats (p8_stats_flush)
+template <int BM, int BN, int WNW, bool AK, bool BK, bool STATS = false>
 __global__ void __launch_bounds__(128 * WNW, (BM == 256 ? 1 : BM == 128 ? 2 : 3))
 gemm8p_kernel(P8Args a, Epi ep) {
-  gemm8p_body<BM, BN, WNW, AK, BK>(a, ep, xcd_remap(blockIdx.x, gridDim.x), blockIdx.z);
+  gemm8p_body<BM, BN, WNW, AK, BK, 1, STATS>(a, ep, xcd_remap(blockIdx.x, gridDim.x), blockIdx.z);
 }
 
 // One launcher per kernel variant. Each variant is explicitly instantiated
 // in a translation unit of its own (csrc/kernels/gemm8p_*.hip): co-compiled
 // instantiations of one kernel template share register-allocation context
 // and perturb each other's code (cdna_hip_programming.md §5.4 rule 19).
-template <int BM, int BN, int WNW, bool AK, bool BK>
+template <int BM, int BN, int WNW, bool AK, bool BK, bool STATS = false>
 void p8_launch_one(const P8Args& g, const Epi& ep, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemm8p_kernel<BM, BN, WNW, AK, BK>), grid, dim3(P8Geo<BM, BN, WNW>::THREADS), 0, s,
+  hipLaunchKernelGGL((gemm8p_kernel<BM, BN, WNW, AK, BK, STATS>), grid, dim3(P8Geo<BM, BN, WNW>::THREADS), 0, s,
                      g, ep);
 }
 
@@ -541,6 +614,25 @@ void p8_launch_one(const P8Args& g, const Epi& ep, dim3 grid, hipStream_t s) {
   template void p8_launch_ks2<BM, BN, W, AK, BK>(const P8Args&, const Epi&, dim3, hipStream_t);
 #define TAM_P8_INST(BM, BN, W, AK, BK) \
   template void p8_launch_one<BM, BN, W, AK, BK>(const P8Args&, const Epi&, dim3, hipStream_t);
+
+// the statistics variants (K-major A and B only, one TU each: gemm8p_*_kk_st.hip)
+#define TAM_P8_ST_VARIANTS(X) X(256, 256, 4) X(128, 128, 2) X(64, 128, 2)
+#define TAM_P8_ST_EXTERN(BM, BN, W) \
+  extern template void p8_launch_one<BM, BN, W, true, true, true>(const P8Args&, const Epi&, dim3, hipStream_t);
+#define TAM_P8_ST_INST(BM, BN, W) \
+  template void p8_launch_one<BM, BN, W, true, true, true>(const P8Args&, const Epi&, dim3, hipStream_t);
+#define TAM_P8_KS2_ST_VARIANTS(X) X(64, 128, 2) X(128, 128, 2)
+#define TAM_P8_KS2_ST_EXTERN(BM, BN, W) \
+  extern template void p8_launch_ks2<BM, BN, W, true, true, true>(const P8Args&, const Epi&, dim3, hipStream_t);
+#define TAM_P8_KS2_ST_INST(BM, BN, W) \
+  template void p8_launch_ks2<BM, BN, W, true, true, true>(const P8Args&, const Epi&, dim3, hipStream_t);
+
+// Epi::stats on the gemm8p bf16-store path: K-major operands, one K slice, a
+// plain 16-B-chunk bf16 store (launch_gemm8p refuses anything else loudly)
+inline bool gemm8p_stats_ok(bool ak, bool bk, int N, const Epi& ep, int splits) {
+  return ak && bk && splits <= 1 && !ep.c_f32 && ep.mode == 0 && !ep.mask && !ep.bnx && N % 8 == 0 &&
+         (ep.ldc & 7) == 0 && (((uintptr_t)ep.c) & 15) == 0;
+}
 
 // shape / layout conditions of the LDS-DMA kernels (tile >= 128)
 inline bool gemm8p_ok(bool ak, bool bk, int M, int N, int K, long lda, long ldb) {

@@ -70,9 +70,33 @@ void gemm_skinny_policy(int on, int force_splits, int nst);
 
 // NHWC convolutions, weights [K][R][S][C] (C, K multiples of 8)
 // ws / ws_floats: split-K scratch of conv_*_split_ws(g) floats (none: unsplit)
+// pw_tile (pointwise convs the gemm8p route accepts, conv_pw_gemm_kind): -2
+// the measured route table decides (default), 0 the conv paths, > 0 that
+// gemm8p tile (the route timing and tests)
 int conv_fwd(const bf16_t* x, const bf16_t* w, const ConvGeom& g, Epi ep, hipStream_t s, float* ws = nullptr,
-             long ws_floats = 0);
-long conv_fwd_split_ws(const ConvGeom& g);
+             long ws_floats = 0, int pw_tile = -2);
+// ep given: 0 also when the pass takes the gemm8p pointwise route (no slab scratch)
+long conv_fwd_split_ws(const ConvGeom& g, const Epi* ep = nullptr);
+// Stage 2-4 pointwise (1x1 / stride-1 / pad-0) convs as plain K-major GEMMs
+// Y[M][N] = X[M][K] . W[N][K]^T on the gemm8p core, forward (BN statistics in
+// its epilogue) and dgrad on the re-laid weight (ReLU-backward mask), routed
+// per (M, N, K, epilogue kind) by measurement against the LDS-DMA conv core.
+// kind: 0 plain, 1 relu, 2 stats, 3 stats + relu, 4 mask; -1: not a candidate
+// (another epilogue, a shape gemm_pw takes or gemm8p cannot, or switched off)
+int conv_pw_gemm_kind(int M, int N, int K, const Epi& ep);
+// the route of a candidate: > 0 the gemm8p tile code, 0 the conv core, -1 not
+// measured yet (the conv core runs; the op binding times it outside capture)
+int conv_pw_route_get(int M, int N, int K, int kind);
+struct ConvPwRoute {
+  int M, N, K, kind, tile;
+  float ms_conv, ms_p8;
+};
+void conv_pw_route_set(const ConvPwRoute& r, bool keep_existing);
+int conv_pw_routes(ConvPwRoute* out, int cap);   // copies up to cap entries, returns the count
+// mode 1: routed (default; TAM_CONV_PW_GEMM), 0: off (the conv core, A/B),
+// 2: every candidate on gemm8p tile `tile` (tests / sweeps)
+void conv_pw_gemm_policy(int mode, int tile);
+int conv_pw_gemm_mode();
 // ResNet stem (7x7 / s2 / p3, C 8 -> K 64) forward kernel; false: not its shape
 bool conv_stem_fwd(const bf16_t* x, const bf16_t* w, const ConvGeom& g, const Epi& ep, hipStream_t s);
 void conv_stem_policy(int p);   // 1: stem kernels where they apply (default), 0: generic paths
@@ -80,11 +104,11 @@ void conv_stem_policy(int p);   // 1: stem kernels where they apply (default), 0
 long conv_stem_wgrad_ws(const ConvGeom& g);
 bool conv_stem_wgrad(const bf16_t* dy, const bf16_t* x, const ConvGeom& g, float* dw, int mode, float* ws,
                      long ws_floats, hipStream_t s);
-long conv_dgrad_split_ws(const ConvGeom& g);
+long conv_dgrad_split_ws(const ConvGeom& g, const Epi* ep = nullptr);
 void conv_split_policy(int p);   // 1: split-K of under-filled LDS-DMA passes (default), 0: off
 // dx[N*H*W][C]; wt = conv_weight_t(w) laid out [C][R][S][K] (ignored for 1x1/s1)
 int conv_dgrad(const bf16_t* dy, const bf16_t* w, const bf16_t* wt, const ConvGeom& g, Epi ep,
-               hipStream_t s, float* ws = nullptr, long ws_floats = 0);
+               hipStream_t s, float* ws = nullptr, long ws_floats = 0, int pw_tile = -2);
 // dw[K][R*S*C] fp32, ep.mode 0 (overwrite) or 1 (accumulate)
 // ws / ws_floats: slab split-K scratch of conv_wgrad_split_ws(g) floats (none: atomics)
 int conv_wgrad(const bf16_t* dy, const bf16_t* x, const ConvGeom& g, Epi ep, hipStream_t s,

@@ -9,10 +9,14 @@
 //          split-K over output pixels with fp32 atomics)
 // 1x1 / stride-1 / pad-0 convolutions go straight to the dense GEMM.
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <tuple>
 
 #include "tam/launch.h"
 #include "tam/tiles.h"
 #include "tam/conv_dma.h"
+#include "tam/gemm8p.h"
 #include "tam/kernels.h"
 
 namespace tam {
@@ -56,16 +60,84 @@ static bool is_pointwise(const ConvGeom& g) {
   return g.R == 1 && g.S == 1 && g.stride == 1 && g.pad == 0;
 }
 
+// ---- pointwise convs on the gemm8p core (launch.h). ResNet-50's stage 2-4
+// 1x1 / stride-1 convs (M = 50176 / 12544 / 3136 pixels at batch 64, K and N
+// in 128..2048) are dense K-major GEMMs, forward and -- on the re-laid
+// weight -- dgrad; the implicit-GEMM core's row gather, 3x3-tuned cost model
+// and slab split-K buy them nothing. TAM_CONV_PW_GEMM=0: the conv core (A/B)
+static int g_conv_pw_gemm = [] {
+  const char* e = getenv("TAM_CONV_PW_GEMM");
+  return e ? atoi(e) : 1;
+}();
+static int g_conv_pw_gemm_tile = 0;
+TAM_KNOB(g_conv_pw_gemm) TAM_KNOB(g_conv_pw_gemm_tile)
+void conv_pw_gemm_policy(int mode, int tile) {
+  g_conv_pw_gemm = mode;
+  g_conv_pw_gemm_tile = tile;
+}
+int conv_pw_gemm_mode() { return g_conv_pw_gemm; }
+
+static std::map<std::tuple<int, int, int, int>, ConvPwRoute> g_pw_routes;
+static std::mutex g_pw_mu;
+
+int conv_pw_gemm_kind(int M, int N, int K, const Epi& ep) {
+  if (!g_conv_pw_gemm || ep.c_f32 || ep.mode != 0 || ep.bias || ep.alpha != 1.f || ep.bnx || ep.colsum_a) return -1;
+  if (ep.mask && (ep.relu || ep.stats)) return -1;
+  if (!gemm8p_ok(true, true, M, N, K, K, K) || gemm_pw_ok(M, N, K, K, K, ep.ldc)) return -1;
+  // the 16-B chunk store (and mask read) path of the gemm8p epilogue
+  if (N % 8 != 0 || (ep.ldc & 7) != 0 || (((uintptr_t)ep.c) & 15) != 0) return -1;
+  if (ep.mask && ((ep.ldm & 7) != 0 || (((uintptr_t)ep.mask) & 15) != 0)) return -1;
+  if (ep.mask) return 4;
+  return (ep.stats ? 2 : 0) + (ep.relu ? 1 : 0);
+}
+
+int conv_pw_route_get(int M, int N, int K, int kind) {
+  std::lock_guard<std::mutex> g(g_pw_mu);
+  auto it = g_pw_routes.find({M, N, K, kind});
+  return it == g_pw_routes.end() ? -1 : it->second.tile;
+}
+
+void conv_pw_route_set(const ConvPwRoute& r, bool keep_existing) {
+  std::lock_guard<std::mutex> g(g_pw_mu);
+  const std::tuple<int, int, int, int> key{r.M, r.N, r.K, r.kind};
+  if (keep_existing && g_pw_routes.count(key)) return;
+  g_pw_routes[key] = r;
+}
+
+int conv_pw_routes(ConvPwRoute* out, int cap) {
+  std::lock_guard<std::mutex> g(g_pw_mu);
+  int n = 0;
+  for (const auto& kv : g_pw_routes) {
+    if (n < cap) out[n] = kv.second;
+    ++n;
+  }
+  return n;
+}
+
+// the gemm8p tile a pointwise pass runs on (0: the conv paths)
+static int conv_pw_tile(int M, int N, int K, const Epi& ep, int pw_tile) {
+  if (pw_tile == 0) return 0;
+  // (the conv-core test policies 0 / 2 / 3 keep their shapes on the cores they test)
+  if (g_conv_dma != 1 && pw_tile < 0 && g_conv_pw_gemm < 2) return 0;
+  const int kind = conv_pw_gemm_kind(M, N, K, ep);
+  if (kind < 0) return 0;
+  int t = pw_tile > 0 ? pw_tile : g_conv_pw_gemm >= 2 ? g_conv_pw_gemm_tile : conv_pw_route_get(M, N, K, kind);
+  if (t == 256 && (M < 256 || N < 256)) t = 128;
+  return t == 64 || t == 65 || t == 128 || t == 129 || t == 256 ? t : 0;
+}
+
 // returns 1 when the path taken accumulated the BN statistics into ep.stats
 // (0: none; the BN then reduces the output itself)
 // split-K scratch (floats) conv_fwd / conv_dgrad would use on the LDS-DMA
 // core for this geometry (0: the pass runs unsplit); the caller allocates it
-long conv_fwd_split_ws(const ConvGeom& g) {
+long conv_fwd_split_ws(const ConvGeom& g, const Epi* ep) {
   if (!g_conv_dma || g.dil != 1 || !g_conv_split) return 0;
+  if (ep && is_pointwise(g) && conv_pw_tile(g.N * g.P * g.Q, g.K, g.C, *ep, -2)) return 0;
   return conv_dma_split_ws(cd_fwd_args(nullptr, nullptr, g), g_conv_dma >= 2 ? g_conv_dma - 1 : 0);
 }
-long conv_dgrad_split_ws(const ConvGeom& g) {
+long conv_dgrad_split_ws(const ConvGeom& g, const Epi* ep) {
   if (!g_conv_dma || g.dil != 1 || g.stride != 1 || !g_conv_split) return 0;
+  if (ep && is_pointwise(g) && conv_pw_tile(g.N * g.H * g.W, g.C, g.K, *ep, -2)) return 0;
   CDArgs a = cd_dgrad_args(nullptr, nullptr, g, 0, 0);
   const int force = g_conv_dma >= 2 ? g_conv_dma - 1 : (g.C == 64 && a.M >= (1L << 20) ? 1 : 0);
   return conv_dma_split_ws(a, force);
@@ -78,7 +150,7 @@ long conv_dgrad_split_ws(const ConvGeom& g) {
 // fallback gets a separate bn_stats pass)
 
 int conv_fwd(const bf16_t* x, const bf16_t* w, const ConvGeom& g, Epi ep, hipStream_t s, float* ws,
-             long ws_floats) {
+             long ws_floats, int pw_tile) {
   const int M = g.N * g.P * g.Q, Kd = g.R * g.S * g.C;
   if (conv_stem_fwd(x, w, g, ep, s)) return ep.stats ? 1 : 0;   // 7x7/s2 8->64 stem (conv_stem.hip)
   // pointwise convs over many pixels (ResNet-50's 56x56 bottleneck 1x1s):
@@ -86,6 +158,14 @@ int conv_fwd(const bf16_t* x, const bf16_t* w, const ConvGeom& g, Epi ep, hipStr
   if (is_pointwise(g) && !ep.c_f32 && ep.mode == 0 && !ep.bias && !ep.mask && ep.alpha == 1.f &&
       gemm_pw(x, g.C, w, g.C, (bf16_t*)ep.c, ep.ldc, M, g.K, g.C, nullptr, 0, ep.stats, ep.relu, s))
     return ep.stats ? 1 : 0;
+  // the other pointwise convs (stages 2-4): the gemm8p tile the route table
+  // measured faster than the conv core, BN statistics in its epilogue
+  if (is_pointwise(g)) {
+    if (const int t = conv_pw_tile(M, g.K, g.C, ep, pw_tile)) {
+      launch_gemm8p(x, g.C, true, w, g.C, true, M, g.K, g.C, ep, 1, s, t);
+      return ep.stats ? 1 : 0;
+    }
+  }
   if (g_conv_dma && g.dil == 1) {
     CDArgs a = cd_fwd_args(x, w, g);
     if (g_conv_halo && launch_conv_halo(a, ep, s)) return ep.stats ? 1 : 0;
@@ -123,8 +203,16 @@ static void dgrad_tile(const bf16_t* dy, const bf16_t* wt, const ConvGeom& g, co
 // ep.stats -- only the single-launch stride-1 LDS-DMA path produces them;
 // every other path clears ep.stats and returns 0
 int conv_dgrad(const bf16_t* dy, const bf16_t* w, const bf16_t* wt, const ConvGeom& g, Epi ep,
-               hipStream_t s, float* ws, long ws_floats) {
+               hipStream_t s, float* ws, long ws_floats, int pw_tile) {
   const int M = g.N * g.H * g.W, Kd = g.R * g.S * g.K;
+  // pointwise: dX[M][C] = dY[M][K] . Wt[C][K]^T on the routed gemm8p tile,
+  // ReLU-backward mask in its epilogue
+  if (wt && is_pointwise(g)) {
+    if (const int t = conv_pw_tile(M, g.C, g.K, ep, pw_tile)) {
+      launch_gemm8p(dy, g.K, true, wt, g.K, true, M, g.C, g.K, ep, 1, s, t);
+      return 0;
+    }
+  }
   if (wt && g_conv_dma && g.dil == 1 && g.stride == 1) {
     // rows = dX pixels over an H x W grid, gathered from dY (P x Q x K), B = Wt [C][R][S][K]
     CDArgs a = cd_dgrad_args(dy, wt, g, 0, 0);

@@ -117,6 +117,8 @@ static bool p8_known(int T) { return T == 64 || T == 65 || T == 128 || T == 129 
 
 TAM_P8_VARIANTS(TAM_P8_EXTERN)
 TAM_P8_KS2_VARIANTS(TAM_P8_KS2_EXTERN)
+TAM_P8_ST_VARIANTS(TAM_P8_ST_EXTERN)
+TAM_P8_KS2_ST_VARIANTS(TAM_P8_KS2_ST_EXTERN)
 
 template <int BM, int BN, int WNW>
 static void p8_launch_l(bool ak, bool bk, const P8Args& g, const Epi& ep, dim3 grid, hipStream_t s) {
@@ -147,6 +149,20 @@ void launch_gemm8p(const bf16_t* A, long lda, bool ak, const bf16_t* B, long ldb
   const int z = cdiv(ktiles, kps);
   P8Args g{A, lda, B, ldb, M, N, K, kps, g_p8_group};
   const dim3 grid(tiles, 1, z);
+  if (ep.stats) {
+    // BatchNorm statistics of the stored output (a pointwise conv's forward):
+    // the STATS instantiations; no other gemm8p epilogue accumulates them
+    if (!gemm8p_stats_ok(ak, bk, N, ep, z)) {
+      fprintf(stderr, "launch_gemm8p: Epi::stats needs K-major operands, one K slice and a plain bf16 store\n");
+      abort();
+    }
+    if (T == 65) p8_launch_ks2<64, 128, 2, true, true, true>(g, ep, grid, s);
+    else if (T == 129) p8_launch_ks2<128, 128, 2, true, true, true>(g, ep, grid, s);
+    else if (T == 64) p8_launch_one<64, 128, 2, true, true, true>(g, ep, grid, s);
+    else if (T == 128) p8_launch_one<128, 128, 2, true, true, true>(g, ep, grid, s);
+    else p8_launch_one<256, 256, 4, true, true, true>(g, ep, grid, s);
+    return;
+  }
   if (T == 65) {
     if (bk) p8_launch_ks2<64, 128, 2, true, true>(g, ep, grid, s);
     else p8_launch_ks2<64, 128, 2, true, false>(g, ep, grid, s);

@@ -50,7 +50,7 @@ def main():
     keys = []
     for ln in _lib.routes_file().read_text().splitlines():
         p = ln.split()
-        if len(p) < 8:
+        if len(p) < 8 or p[3] == "PW":     # (PW: pointwise-conv routes, tools/bench_pw_route.py)
             continue
         M, N, K = int(p[0]), int(p[1]), int(p[2])
         keys.append((M, N, K, p[3][0] == "K", p[3][1] == "K", int(p[4]), p[5] == "1", p[7]))
