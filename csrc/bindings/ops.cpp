@@ -1335,6 +1335,72 @@ void grad_clip_finalize_op(const Tensor& partials, double max_norm, double gscal
                           const_cast<float*>(clip_ptr(clip, partials)), cur_stream(partials));
 }
 int64_t grad_sumsq_blocks_op(int64_t n) { return tam::grad_sumsq_blocks((long)n); }
+// layer-wise trust ratio (optim.hip): tiles int32 [ntiles][4], seg_first int32
+// [nseg + 1], partials float64 [ntiles][2], ratios float32 [nseg][3]. Returns
+// the decayed extent; the kernels bound-check every tile record against it
+static long check_trust(const Tensor& w, std::initializer_list<const Tensor*> same, const Tensor& wb, double eta,
+                        const Tensor& tiles, const Tensor& seg_first, const Tensor& partials, const Tensor& ratios,
+                        int64_t zero_from, int64_t wd_until, const char* op) {
+  check_f32(w, "w"); check_contig(w, "w"); check_bf16(wb, "wb"); check_contig(wb, "wb");
+  const int64_t n = w.numel();
+  TORCH_CHECK(n % 64 == 0 && n < (1LL << 31) && wb.numel() == n && wb.device() == w.device(), op,
+              ": numel % 64, below 2^31, and a shadow of the same size");
+  TORCH_CHECK((((uintptr_t)w.data_ptr()) & 15) == 0 && (((uintptr_t)wb.data_ptr()) & 7) == 0, op,
+              ": w must be 16-B aligned, wb 8-B aligned");
+  for (const Tensor* t : same) {
+    check_f32(*t, "g / state"); check_contig(*t, "g / state");
+    TORCH_CHECK(t->numel() == n && t->device() == w.device() && (((uintptr_t)t->data_ptr()) & 15) == 0, op,
+                ": g and the state must be 16-B aligned float32 tensors of w's size on its device");
+  }
+  TORCH_CHECK(std::isfinite(eta) && eta > 0.0, op, ": eta must be a finite number > 0, got ", eta);
+  const int64_t nd = wd_until < 0 ? n : wd_until;
+  TORCH_CHECK(nd <= n && nd % 64 == 0, op, ": wd_until must be a tile boundary (a multiple of 64) inside the arena, got ",
+              wd_until);
+  TORCH_CHECK(zero_from >= 0 && zero_from % 4 == 0, op, ": zero_from % 4");
+  check_dev(tiles, "tiles"); check_contig(tiles, "tiles"); check_dev(seg_first, "seg_first");
+  check_contig(seg_first, "seg_first");
+  TORCH_CHECK(tiles.scalar_type() == at::kInt && seg_first.scalar_type() == at::kInt &&
+                  tiles.device() == w.device() && seg_first.device() == w.device(), op,
+              ": tiles / seg_first must be int32 tensors on the parameters' device");
+  TORCH_CHECK(tiles.numel() % 4 == 0 && (((uintptr_t)tiles.data_ptr()) & 15) == 0 && seg_first.numel() >= 1, op,
+              ": tiles must be [ntiles][4], 16-B aligned; seg_first [nseg + 1]");
+  const int64_t nt = tiles.numel() / 4, ns = seg_first.numel() - 1;
+  TORCH_CHECK(nd == 0 || (nt >= 1 && ns >= 1), op, ": a decayed region needs at least one tile and one segment");
+  TORCH_CHECK(nt <= (1 << 24) && ns <= nt, op, ": ", nt, " tiles, ", ns, " segments");
+  check_dev(partials, "partials"); check_contig(partials, "partials");
+  TORCH_CHECK(partials.scalar_type() == at::kDouble && partials.device() == w.device() && partials.numel() >= 2 * nt,
+              op, ": partials must be float64 [ntiles][2] on the parameters' device");
+  check_f32(ratios, "ratios"); check_contig(ratios, "ratios");
+  TORCH_CHECK(ratios.device() == w.device() && ratios.numel() >= 3 * ns, op, ": ratios holds ", ratios.numel(),
+              " floats, ", ns, " segments need ", 3 * ns);
+  return (long)nd;
+}
+void lars_op(const Tensor& w, const Tensor& g, const Tensor& mom, const Tensor& wb, double lr, double momentum,
+             double wd, double eta, double gscale, const Tensor& tiles, const Tensor& seg_first,
+             const Tensor& partials, const Tensor& ratios, const optional<Tensor>& guard, int64_t zero_from,
+             int64_t wd_until, const optional<Tensor>& clip) {
+  const long nd = check_trust(w, {&g, &mom}, wb, eta, tiles, seg_first, partials, ratios, zero_from, wd_until,
+                              "tam.lars_step");
+  tam::lars_step(w.data_ptr<float>(), g.data_ptr<float>(), mom.data_ptr<float>(), bpm(wb), w.numel(), (float)lr,
+                 (float)momentum, (float)wd, (float)eta, (float)gscale, tiles.data_ptr<int>(),
+                 (int)(tiles.numel() / 4), seg_first.data_ptr<int>(), (int)seg_first.numel() - 1,
+                 partials.data_ptr<double>(), ratios.data_ptr<float>(), cur_stream(w), guard_ptr(guard, w),
+                 (long)zero_from, nd, clip_ptr(clip, w));
+}
+void lamb_op(const Tensor& w, const Tensor& g, const Tensor& m, const Tensor& v, const Tensor& wb, double lr,
+             double b1, double b2, double eps, double wd, int64_t step, double eta, double gscale,
+             const Tensor& tiles, const Tensor& seg_first, const Tensor& partials, const Tensor& ratios,
+             const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until, const optional<Tensor>& clip) {
+  const long nd = check_trust(w, {&g, &m, &v}, wb, eta, tiles, seg_first, partials, ratios, zero_from, wd_until,
+                              "tam.lamb_step");
+  TORCH_CHECK(step >= 1 && step <= 0x7fffffffLL, "tam.lamb_step: step must be a 1-based optimizer step, got ", step);
+  tam::lamb_step(w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(), v.data_ptr<float>(), bpm(wb),
+                 w.numel(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (int)step, (float)eta,
+                 (float)gscale, tiles.data_ptr<int>(), (int)(tiles.numel() / 4), seg_first.data_ptr<int>(),
+                 (int)seg_first.numel() - 1, partials.data_ptr<double>(), ratios.data_ptr<float>(), cur_stream(w),
+                 guard_ptr(guard, w), (long)zero_from, nd, clip_ptr(clip, w));
+}
+int64_t trust_tile_op() { return tam::trust_tile(); }
 void lstm_guard_step_op(const Tensor& err) {
   TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 2,
               "tam.lstm_guard_step: err must be an int32 [2] GPU tensor");
@@ -1601,6 +1667,9 @@ TORCH_LIBRARY(tam, m) {
   m.def("grad_sumsq(Tensor g, Tensor(a!) partials) -> ()", &grad_sumsq_op);
   m.def("grad_clip_finalize(Tensor partials, float max_norm, float gscale, Tensor(a!) clip) -> ()", &grad_clip_finalize_op);
   m.def("grad_sumsq_blocks(int n) -> int", &grad_sumsq_blocks_op);
+  m.def("lars_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float eta, float gscale, Tensor tiles, Tensor seg_first, Tensor(e!) partials, Tensor(f!) ratios, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &lars_op);
+  m.def("lamb_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float eta, float gscale, Tensor tiles, Tensor seg_first, Tensor(f!) partials, Tensor(g!) ratios, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &lamb_op);
+  m.def("trust_tile() -> int", &trust_tile_op);
   m.def("lstm_guard_step(Tensor(a!) err) -> ()", &lstm_guard_step_op);
   m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_forward_op);
   m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_backward_op);

@@ -169,6 +169,27 @@ int grad_sumsq_blocks(long n);   // blocks grad_sumsq launches over n elements (
 void grad_sumsq(const float* g, long n, double* partials, int slots, hipStream_t s);
 void grad_clip_finalize(const double* partials, int slots, float max_norm, float gscale, float* clip,
                         hipStream_t s);
+// layer-wise trust ratio (LARS over SGD momentum, LAMB over AdamW; optim.hip
+// "layer-wise trust ratio"). The decayed region [0, wd_until) is cut by the
+// host into tiles of at most trust_tile() elements, each inside one segment
+// (= one parameter's padded extent): tiles int32 [ntiles][4] = {start, length,
+// segment, 0} (elements, multiples of 64), seg_first int32 [nseg + 1] = first
+// tile of every segment (+ ntiles). Three launches on s, no host read:
+// per-tile fp64 sums of squares -> partials [ntiles][2]; per-segment ratio ->
+// ratios float [nseg][3] = {ratio, ||w||, ||g * gscale|| (LARS) or ||u||
+// (LAMB)}; the streaming update with the tile's ratio. [wd_until, n) runs
+// sgd_step / adam_step on the slice with wd = 0 (ratio 1). guard / clip as in
+// the plain steps: a skipped step writes no weights, state, shadow or ratios
+// and resets the gradient from zero_from on.
+int trust_tile();
+void lars_step(float* w, float* g, float* mom, bf16_t* wb, long n, float lr, float momentum, float wd, float eta,
+               float gscale, const int* tiles, int ntiles, const int* seg_first, int nseg, double* partials,
+               float* ratios, hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0,
+               long wd_until = -1, const float* clip = nullptr);
+void lamb_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float lr, float b1, float b2, float eps,
+               float wd, int step, float eta, float gscale, const int* tiles, int ntiles, const int* seg_first,
+               int nseg, double* partials, float* ratios, hipStream_t s, const unsigned* guard = nullptr,
+               long zero_from = 0, long wd_until = -1, const float* clip = nullptr);
 
 // fused attention (bf16, head_dim 64): element (b, s, h, d) at b * *_bstride +
 // s * *_stride + 64 h + d (batch-major [B][S][H][64], or a time-major

@@ -561,6 +561,346 @@ void grad_clip_finalize(const double* partials, int slots, float max_norm, float
   hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, s, partials, slots, max_norm, gscale, clip);
 }
 
+// ---------------------------------------------------- layer-wise trust ratio
+// LARS (over SGD momentum) and LAMB (over AdamW) for the decayed region
+// [0, n_decay) of an arena; the no-decay tail runs sgd_step / adam_step on
+// its slice (ratio 1, wd 0). A segment is one parameter's padded extent; the
+// host cuts every segment into tiles of at most kTrustTile elements (a
+// multiple of 64, a segment's last tile may be short) and passes
+//   tiles     int4 [ntiles]   {start, length, segment, 0}, elements
+//   seg_first int  [nseg + 1] first tile of every segment, then ntiles
+// Contract (||.|| = L2 norm over the segment, fp64 sums; g^ = g * gscale,
+// gscale including the clip scale):
+//   LARS  r = eta |w| / (|g^| + wd |w|);  d = r (g^ + wd w);
+//         mom = momentum mom + d;  w -= lr mom
+//   LAMB  m, v, m^, v^ as adam_stream_kernel;  u = m^ / (sqrt(v^) + eps) + wd w;
+//         r = eta |w| / |u|;  w -= (lr r) u       (r = 1: the Adam step, bitwise)
+//   r = 1 unless both norms are finite and > 0. The quotient is formed in
+//   fp64 and rounded once to fp32, as grad_clip_finalize's scale is.
+// Pass 1 (blocks stride over TILES on the optimizer's grid): one block reduces
+//   a tile's w^2 and g^^2 / u^2 in fp64 -- lane-local sums over a fixed
+//   element -> thread map, wave shuffles, four wave sums through LDS -- and
+//   stores the pair into the TILE's slot: the order depends on the tile
+//   alone, so the norms do not depend on the grid. No atomics. The LAMB form
+//   also stores the new m / v (pass 3 reads them back; the gradient is not
+//   read again) and resets the gradient.
+// Pass 2 (one wave per segment): lane l sums the segment's tiles l, l + 64,
+//   ... in tile order, the 64 lane sums fold by shuffles; writes
+//   ratios[seg] = {r, |w|, |g^| or |u|}.
+// Pass 3 (blocks stride over tiles): the streaming update with the tile's
+//   ratio, NT 16-B accesses as the streaming kernels above.
+// A tile record that does not lie inside [0, n_decay) / [0, nseg) is skipped
+// by every pass (nothing is read or written through it).
+// Skipped step (guard word / negative clip scale): passes 1 and 2 return,
+// pass 3 resets the gradient from zero_from on; nothing else is written.
+constexpr int kTrustTile = 8192;   // elements: 256 threads x 8 float4 groups
+int trust_tile() { return kTrustTile; }
+
+__device__ __forceinline__ bool step_skipped(const unsigned* guard, const float* clip) {
+  return (guard != nullptr && *guard != 0u) || (clip != nullptr && clip[0] < 0.f);
+}
+__device__ __forceinline__ bool trust_tile_ok(int4 t, long n_decay, int nseg) {
+  return t.x >= 0 && t.y > 0 && t.y <= kTrustTile && ((t.x | t.y) & 63) == 0 && (long)t.x + t.y <= n_decay &&
+         t.z >= 0 && t.z < nseg;
+}
+// the LAMB update direction; passes 1 and 3 both call it on the same values
+__device__ __forceinline__ float lamb_u(float w, float m, float v, float ib1, float ib2, float eps, float wd) {
+  const float mh = m * ib1, vh = v * ib2;
+  return __builtin_fmaf(wd, w, mh / (sqrtf(vh) + eps));
+}
+struct Sq4 {
+  double a0 = 0., a1 = 0., a2 = 0., a3 = 0.;
+  __device__ __forceinline__ void add(float x, float y, float z, float w) {
+    a0 = fma((double)x, (double)x, a0); a1 = fma((double)y, (double)y, a1);
+    a2 = fma((double)z, (double)z, a2); a3 = fma((double)w, (double)w, a3);
+  }
+  __device__ __forceinline__ double sum() const { return (a0 + a1) + (a2 + a3); }
+};
+// block sum of (a, b) into partials[slot]; red: this tile's LDS buffer. One
+// barrier: the caller alternates between two buffers
+__device__ __forceinline__ void tile_store2(double a, double b, double (*red)[2], double* __restrict__ partials,
+                                            int slot) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_down(a, o, 64);
+    b += __shfl_down(b, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6][0] = a;
+    red[threadIdx.x >> 6][1] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[2 * (long)slot] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+    partials[2 * (long)slot + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+  }
+}
+
+__global__ void __launch_bounds__(256) lars_norm_kernel(const float* __restrict__ w, const float* __restrict__ g,
+                                                         const int4* __restrict__ tiles, int ntiles, long n_decay,
+                                                         int nseg, float gscale, double* __restrict__ partials,
+                                                         const unsigned* guard, const float* clip) {
+  if (step_skipped(guard, clip)) return;
+  if (clip != nullptr) gscale *= clip[0];
+  __shared__ double red[2][4][2];
+  constexpr int U = kTrustTile / 4 / 256;
+  int par = 0;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x, par ^= 1) {
+    const int4 tl = tiles[t];
+    Sq4 sw, sg;
+    if (trust_tile_ok(tl, n_decay, nseg)) {
+      const long b4 = tl.x / 4;
+      const int len4 = tl.y / 4;
+      // ordinary loads: pass 3 reads the same bytes next
+      float4 wv[U], gv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = threadIdx.x + u * 256;
+        wv[u] = gv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < len4) {
+          wv[u] = ((const float4*)w)[b4 + i];
+          gv[u] = ((const float4*)g)[b4 + i];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        sw.add(wv[u].x, wv[u].y, wv[u].z, wv[u].w);
+        sg.add(gv[u].x * gscale, gv[u].y * gscale, gv[u].z * gscale, gv[u].w * gscale);
+      }
+    }
+    tile_store2(sw.sum(), sg.sum(), red[par], partials, t);
+  }
+}
+
+__global__ void __launch_bounds__(256) lamb_moments_kernel(
+    const float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+    const int4* __restrict__ tiles, int ntiles, long n_decay, int nseg, float b1, float b2, float eps, float wd,
+    float bc1, float bc2, float gscale, long zero_from4, double* __restrict__ partials, const unsigned* guard,
+    const float* clip) {
+  if (step_skipped(guard, clip)) return;
+  if (clip != nullptr) gscale *= clip[0];
+  const float ib1 = 1.f / bc1, ib2 = 1.f / bc2;
+  __shared__ double red[2][4][2];
+  constexpr int U = 4;
+  int par = 0;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x, par ^= 1) {
+    const int4 tl = tiles[t];
+    Sq4 sw, su;
+    if (trust_tile_ok(tl, n_decay, nseg)) {
+      const long b4 = tl.x / 4;
+      const int len4 = tl.y / 4;
+      for (int base = threadIdx.x; base < len4; base += U * 256) {
+        float4 wv[U], gv[U], mv[U], vv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int i = base + u * 256;
+          wv[u] = gv[u] = mv[u] = vv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (i < len4) {
+            wv[u] = ((const float4*)w)[b4 + i];
+            gv[u] = ld4<U, true>(g, b4 + i);
+            mv[u] = ((const float4*)m)[b4 + i];
+            vv[u] = ((const float4*)v)[b4 + i];
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int i = base + u * 256;
+          if (i >= len4) continue;
+          const float* wp = (const float*)&wv[u]; const float* gp = (const float*)&gv[u];
+          float* mp = (float*)&mv[u]; float* vp = (float*)&vv[u];
+          float us[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const float gr = gp[k] * gscale;
+            mp[k] = __builtin_fmaf(b1, mp[k], (1.f - b1) * gr);
+            vp[k] = __builtin_fmaf(b2, vp[k], (1.f - b2) * gr * gr);
+            us[k] = lamb_u(wp[k], mp[k], vp[k], ib1, ib2, eps, wd);
+          }
+          sw.add(wp[0], wp[1], wp[2], wp[3]);
+          su.add(us[0], us[1], us[2], us[3]);
+          ((float4*)m)[b4 + i] = mv[u];
+          ((float4*)v)[b4 + i] = vv[u];
+          if (b4 + i >= zero_from4) st4<true>(g, b4 + i, make_float4(0.f, 0.f, 0.f, 0.f));
+        }
+      }
+    }
+    tile_store2(sw.sum(), su.sum(), red[par], partials, t);
+  }
+}
+
+__global__ void __launch_bounds__(64) trust_finalize_kernel(const double* __restrict__ partials,
+                                                             const int* __restrict__ seg_first, int ntiles, int nseg,
+                                                             float eta, float wd, int lamb,
+                                                             float* __restrict__ ratios, const unsigned* guard,
+                                                             const float* clip) {
+  if (step_skipped(guard, clip)) return;
+  const int s = blockIdx.x;
+  if (s >= nseg) return;
+  int a = seg_first[s], b = seg_first[s + 1];
+  if (a < 0) a = 0;
+  if (b > ntiles) b = ntiles;
+  double sw = 0., sx = 0.;
+  for (int t = a + (int)threadIdx.x; t < b; t += 64) {
+    sw += partials[2 * (long)t];
+    sx += partials[2 * (long)t + 1];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sw += __shfl_down(sw, o, 64);
+    sx += __shfl_down(sx, o, 64);
+  }
+  if (threadIdx.x == 0) {
+    const double wn = sqrt(sw), xn = sqrt(sx);
+    double r = 1.;
+    // the quotient in fp64: one rounding into the fp32 ratio
+    if (isfinite(wn) && wn > 0. && isfinite(xn) && xn > 0.)
+      r = lamb ? (double)eta * wn / xn : (double)eta * wn / (xn + (double)wd * wn);
+    ratios[3 * s] = (float)r;
+    ratios[3 * s + 1] = (float)wn;
+    ratios[3 * s + 2] = (float)xn;
+  }
+}
+
+__global__ void __launch_bounds__(256) lars_apply_kernel(float* __restrict__ w, float* __restrict__ g,
+                                                          float* __restrict__ mom, bf16_t* __restrict__ wb,
+                                                          const int4* __restrict__ tiles, int ntiles, long n_decay,
+                                                          int nseg, const float* __restrict__ ratios, float lr,
+                                                          float momentum, float wd, float gscale, long zero_from4,
+                                                          const unsigned* guard, const float* clip) {
+  if (step_skipped(guard, clip)) {
+    const long n4 = n_decay / 4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+      if (i >= zero_from4) st4<true>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  if (clip != nullptr) gscale *= clip[0];
+  constexpr int U = 4;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int4 tl = tiles[t];
+    if (!trust_tile_ok(tl, n_decay, nseg)) continue;
+    const float r = ratios[3 * tl.z];
+    const long b4 = tl.x / 4;
+    const int len4 = tl.y / 4;
+    for (int base = threadIdx.x; base < len4; base += U * 256) {
+      float4 wv[U], gv[U], mv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = base + u * 256;
+        wv[u] = gv[u] = mv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < len4) {
+          wv[u] = ld4<U, true>(w, b4 + i); gv[u] = ld4<U, true>(g, b4 + i); mv[u] = ld4<U, true>(mom, b4 + i);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = base + u * 256;
+        if (i >= len4) continue;
+        float* wp = (float*)&wv[u]; const float* gp = (const float*)&gv[u]; float* mp = (float*)&mv[u];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float d = r * __builtin_fmaf(wd, wp[k], gp[k] * gscale);
+          mp[k] = __builtin_fmaf(momentum, mp[k], d);
+          wp[k] = __builtin_fmaf(-lr, mp[k], wp[k]);
+        }
+        st4<true>(w, b4 + i, wv[u]); st4<true>(mom, b4 + i, mv[u]);
+        if (b4 + i >= zero_from4) st4<true>(g, b4 + i, make_float4(0.f, 0.f, 0.f, 0.f));
+        st2<true>(wb, b4 + i, make_uint2(pack_bf2(wp[0], wp[1]), pack_bf2(wp[2], wp[3])));
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) lamb_apply_kernel(float* __restrict__ w, float* __restrict__ g,
+                                                          const float* __restrict__ m, const float* __restrict__ v,
+                                                          bf16_t* __restrict__ wb, const int4* __restrict__ tiles,
+                                                          int ntiles, long n_decay, int nseg,
+                                                          const float* __restrict__ ratios, float lr, float eps,
+                                                          float wd, float bc1, float bc2, long zero_from4,
+                                                          const unsigned* guard, const float* clip) {
+  if (step_skipped(guard, clip)) {
+    const long n4 = n_decay / 4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x)
+      if (i >= zero_from4) st4<true>(g, i, make_float4(0.f, 0.f, 0.f, 0.f));
+    return;
+  }
+  const float ib1 = 1.f / bc1, ib2 = 1.f / bc2;
+  constexpr int U = 4;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int4 tl = tiles[t];
+    if (!trust_tile_ok(tl, n_decay, nseg)) continue;
+    const float lrr = lr * ratios[3 * tl.z];
+    const long b4 = tl.x / 4;
+    const int len4 = tl.y / 4;
+    for (int base = threadIdx.x; base < len4; base += U * 256) {
+      float4 wv[U], mv[U], vv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = base + u * 256;
+        wv[u] = mv[u] = vv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i < len4) {
+          wv[u] = ld4<U, true>(w, b4 + i); mv[u] = ld4<U, true>(m, b4 + i); vv[u] = ld4<U, true>(v, b4 + i);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = base + u * 256;
+        if (i >= len4) continue;
+        float* wp = (float*)&wv[u]; const float* mp = (const float*)&mv[u]; const float* vp = (const float*)&vv[u];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          wp[k] = __builtin_fmaf(-lrr, lamb_u(wp[k], mp[k], vp[k], ib1, ib2, eps, wd), wp[k]);
+        st4<true>(w, b4 + i, wv[u]);
+        st2<true>(wb, b4 + i, make_uint2(pack_bf2(wp[0], wp[1]), pack_bf2(wp[2], wp[3])));
+      }
+    }
+  }
+}
+
+// blocks of a tile-strided pass: the optimizer's grid cap, at most one block per tile
+static int tgrid(int ntiles) {
+  const int cap = ogrid(1L << 40);
+  return ntiles < cap ? (ntiles < 1 ? 1 : ntiles) : cap;
+}
+
+void lars_step(float* w, float* g, float* mom, bf16_t* wb, long n, float lr, float momentum, float wd, float eta,
+               float gscale, const int* tiles, int ntiles, const int* seg_first, int nseg, double* partials,
+               float* ratios, hipStream_t s, const unsigned* guard, long zero_from, long wd_until,
+               const float* clip) {
+  const long nd = wd_until < 0 ? n : wd_until;
+  if (nd > 0 && ntiles > 0 && nseg > 0) {
+    const dim3 grid(tgrid(ntiles));
+    hipLaunchKernelGGL(lars_norm_kernel, grid, dim3(256), 0, s, w, g, (const int4*)tiles, ntiles, nd, nseg, gscale,
+                       partials, guard, clip);
+    hipLaunchKernelGGL(trust_finalize_kernel, dim3(nseg), dim3(64), 0, s, partials, seg_first, ntiles, nseg, eta, wd,
+                       0, ratios, guard, clip);
+    hipLaunchKernelGGL(lars_apply_kernel, grid, dim3(256), 0, s, w, g, mom, wb, (const int4*)tiles, ntiles, nd, nseg,
+                       ratios, lr, momentum, wd, gscale, zero_from / 4, guard, clip);
+  }
+  if (nd < n)
+    sgd_step(w + nd, g + nd, mom + nd, wb + nd, n - nd, lr, momentum, 0.f, gscale, 0, 1, s, guard,
+             zero_from > nd ? zero_from - nd : 0, -1, clip);
+}
+
+void lamb_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float lr, float b1, float b2, float eps,
+               float wd, int step, float eta, float gscale, const int* tiles, int ntiles, const int* seg_first,
+               int nseg, double* partials, float* ratios, hipStream_t s, const unsigned* guard, long zero_from,
+               long wd_until, const float* clip) {
+  const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+  const long nd = wd_until < 0 ? n : wd_until;
+  if (nd > 0 && ntiles > 0 && nseg > 0) {
+    const dim3 grid(tgrid(ntiles));
+    hipLaunchKernelGGL(lamb_moments_kernel, grid, dim3(256), 0, s, w, g, m, v, (const int4*)tiles, ntiles, nd, nseg,
+                       b1, b2, eps, wd, bc1, bc2, gscale, zero_from / 4, partials, guard, clip);
+    hipLaunchKernelGGL(trust_finalize_kernel, dim3(nseg), dim3(64), 0, s, partials, seg_first, ntiles, nseg, eta, wd,
+                       1, ratios, guard, clip);
+    hipLaunchKernelGGL(lamb_apply_kernel, grid, dim3(256), 0, s, w, g, m, v, wb, (const int4*)tiles, ntiles, nd, nseg,
+                       ratios, lr, eps, wd, bc1, bc2, zero_from / 4, guard, clip);
+  }
+  if (nd < n)
+    adam_step(w + nd, g + nd, m + nd, v + nd, wb + nd, n - nd, lr, b1, b2, eps, 0.f, step, gscale, 1, s, guard,
+              zero_from > nd ? zero_from - nd : 0, -1, clip);
+}
+
 __global__ void lstm_guard_step_kernel(unsigned* err) {
   if (threadIdx.x == 0 && err[0] != 0u) {
     err[1] += 1u;

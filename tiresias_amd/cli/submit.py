@@ -8,6 +8,7 @@ Examples::
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --gpus 2 --iterations 800
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model gnmt --duration 30 --grad-clip 5.0
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model transformer --iterations 800 --dropout 0.1 --attn-dropout 0.1
+    python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --gpus 4 --iterations 800 --trust-ratio 0.001
     python -m tiresias_amd.cli.submit --spool /tmp/tam --status
     python -m tiresias_amd.cli.submit --spool /tmp/tam --shutdown
 """
@@ -41,6 +42,9 @@ def main(argv=None) -> int:
                     help="format of the optimizer state: bf16 keeps the moments in bf16 with stochastic "
                          "rounding (4 B per parameter less for Adam, 2 B for SGD, resident and spilled); "
                          "default fp32")
+    ap.add_argument("--trust-ratio", type=float, metavar="ETA",
+                    help="layer-wise adaptive learning rates with trust coefficient ETA > 0: LARS for an SGD "
+                         "model, LAMB for an Adam model; not combined with --opt-dtype bf16")
     ap.add_argument("--status", action="store_true")
     ap.add_argument("--shutdown", action="store_true", help="stop serving once the cluster drains")
     a = ap.parse_args(argv)
@@ -56,7 +60,7 @@ def main(argv=None) -> int:
         ap.error("--model and one of --iterations / --duration are required")
     jid = sp.submit(a.model, a.gpus, iterations=a.iterations, duration=a.duration, job_id=a.job_id,
                     batch=a.batch, grad_clip=a.grad_clip, dropout=a.dropout,
-                    attn_dropout=a.attn_dropout, opt_dtype=a.opt_dtype)
+                    attn_dropout=a.attn_dropout, opt_dtype=a.opt_dtype, trust_ratio=a.trust_ratio)
     print(jid)
     return 0
 

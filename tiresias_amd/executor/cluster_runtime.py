@@ -150,6 +150,7 @@ class ReplayJob:
     dropout: Optional[float] = None      # training dropout of the job (None = off)
     attn_dropout: Optional[float] = None     # attention-probability dropout of the job (None = off)
     opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" (None = fp32)
+    trust_ratio: Optional[float] = None  # layer-wise trust coefficient of the job: LARS / LAMB (None = off)
 
 
 class Controller:
@@ -511,7 +512,7 @@ class Controller:
         now = self.now()
         for req in self.spool.poll():
             try:
-                jid, model, g, iters, batch, clip, drop, adrop, odt = self._validate(req)
+                jid, model, g, iters, batch, clip, drop, adrop, odt, eta = self._validate(req)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -524,7 +525,7 @@ class Controller:
             spec = JobSpec(job_id=jid, submit_time=now, duration=iters * self._iter_est(model, g),
                            num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
-                                        dropout=drop, attn_dropout=adrop, opt_dtype=odt)
+                                        dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -533,8 +534,8 @@ class Controller:
 
     def _validate(self, req: dict):
         """Untrusted spool request -> (job_id, model, num_gpu, iterations,
-        batch, grad_clip, dropout, attn_dropout, opt_dtype); raises ValueError with
-        the rejection reason."""
+        batch, grad_clip, dropout, attn_dropout, opt_dtype, trust_ratio); raises
+        ValueError with the rejection reason."""
         from ..models import MODELS
 
         jid = req.get("job_id")
@@ -589,7 +590,16 @@ class Controller:
         odt = req.get("opt_dtype")
         if odt is not None and (not isinstance(odt, str) or odt not in ("fp32", "bf16")):
             raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', got {odt!r}")
-        return jid, model, g, iters, batch, clip, drop, adrop, odt
+        eta = req.get("trust_ratio")
+        if eta is not None:
+            if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta > 0 or eta == float("inf"):
+                raise ValueError(f"trust_ratio must be a finite number > 0, got {eta!r}")
+            eta = float(eta)
+            if self.ddp_shard and g > 1:
+                raise ValueError("trust_ratio is not supported for a multi-GPU job under ddp_shard")
+            if odt == "bf16":
+                raise ValueError("trust_ratio is not supported with opt_dtype 'bf16'")
+        return jid, model, g, iters, batch, clip, drop, adrop, odt, eta
 
     def status(self) -> dict:
         s = self.sched
@@ -651,7 +661,7 @@ class Controller:
                 act = {"op": "start", "job": j.job_id, "ranks": ranks, "model": rj.model,
                        "iters": max(0, rj.iterations - self.done_iters[j.job_id]),
                        "batch": rj.batch, "grad_clip": rj.grad_clip, "dropout": rj.dropout,
-                       "attn_dropout": rj.attn_dropout, "opt_dtype": rj.opt_dtype,
+                       "attn_dropout": rj.attn_dropout, "opt_dtype": rj.opt_dtype, "trust_ratio": rj.trust_ratio,
                        "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
@@ -893,7 +903,7 @@ class Worker:
         """Warm-pool key of a start action: what fixes a trainer's buffers.
         The optimizer-state format does (bf16 state buffers cannot serve a
         fp32-state job, nor the reverse), so a bf16-state job's key carries it;
-        the per-job setters (clip, dropouts) are not part of the key."""
+        the per-job setters (clip, dropouts, trust ratio) are not part of the key."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
         return key + ("bf16",) if act.get("opt_dtype") == "bf16" else key
 
@@ -922,6 +932,7 @@ class Worker:
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
             t.set_dropout(act.get("dropout"))        # likewise (a change re-captures the graph)
             t.set_attn_dropout(act.get("attn_dropout"))
+            t.set_trust_ratio(act.get("trust_ratio"))    # per job too: its buffers are a few KiB
             self._bind(t, ranks)
             if want and not t.use_graph and t.ddp is None:
                 t.enable_graph()
@@ -929,7 +940,8 @@ class Worker:
         t = Trainer(act["model"], self.device, batch=act.get("batch"), group=self._group(ranks),
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
                     ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
-                    attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"))
+                    attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"),
+                    trust_ratio=act.get("trust_ratio"))
         t.pool_key = key
         return t
 

@@ -166,8 +166,8 @@ class FakeCluster:
                 self.stats["spill_bytes"] += b * len(self.held[job])
                 self.spilled.add(job)
             elif op == "start":
-                # (the per-job recipe keys grad_clip / dropout / attn_dropout
-                # change no cost in the world model: accepted and ignored;
+                # (the per-job recipe keys grad_clip / dropout / attn_dropout /
+                # trust_ratio change no cost in the world model: accepted and ignored;
                 # opt_dtype sizes the state that spills and moves)
                 ranks = tuple(a["ranks"])
                 if len(ranks) > 1 and ranks not in self.groups:

@@ -18,7 +18,8 @@ Request schema (JSON)::
      "grad_clip": null,             # global-norm gradient clip, a number > 0
      "dropout": null,               # training dropout probability, 0 <= p < 1
      "attn_dropout": null,          # attention-probability dropout, 0 <= p < 1 (quantised to 1/256)
-     "opt_dtype": null}             # optimizer-state format, "fp32" or "bf16" (null = fp32)
+     "opt_dtype": null,             # optimizer-state format, "fp32" or "bf16" (null = fp32)
+     "trust_ratio": null}           # layer-wise trust coefficient > 0: LARS (sgd models) / LAMB (adam models)
 """
 from __future__ import annotations
 
@@ -47,14 +48,14 @@ class Spool:
                duration: Optional[float] = None, job_id: Optional[str] = None,
                batch: Optional[int] = None, grad_clip: Optional[float] = None,
                dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
-               opt_dtype: Optional[str] = None) -> str:
+               opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None) -> str:
         if iterations is None and duration is None:
             raise ValueError("give iterations or duration")
         jid = job_id or f"sub-{time.time_ns()}-{os.getpid()}"
         req = {"job_id": jid, "model": model, "num_gpu": int(num_gpu), "iterations": iterations,
                "duration": duration, "batch": batch, "grad_clip": grad_clip, "dropout": dropout,
                "attn_dropout": attn_dropout, "opt_dtype": opt_dtype,
-               "submitted_wall": time.time()}
+               "trust_ratio": trust_ratio, "submitted_wall": time.time()}
         _atomic_write(os.path.join(self.root, "incoming", f"{jid}.json"), req)
         return jid
 

@@ -17,7 +17,7 @@ import torch
 from ..models import MODELS, make_model, samples_per_batch, synthetic_batch
 from ..ops import _lib
 from ..ops import functional as Fx
-from ..ops.arena import Arena
+from ..ops.arena import Arena, _padded, trust_tile_table
 from ..parallel.ddp import GradBucketer
 from ..parallel.gang import comm_rank, comm_size
 
@@ -29,7 +29,7 @@ class Trainer:
                  overlap_wgrad: Optional[bool] = None, branches: Optional[bool] = None,
                  ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
                  dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
-                 opt_dtype: Optional[str] = None):
+                 opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None):
         self.model_name = model
         self.spec = MODELS[model]
         if opt_dtype is None:
@@ -52,6 +52,13 @@ class Trainer:
         if grad_clip is not None and ddp_shard and group is not None and comm_size(group) > 1:
             raise ValueError("grad_clip with ddp_shard is not supported: a sharded gang's global norm needs "
                              "the replicated tails counted once")
+        if trust_ratio is None:
+            trust_ratio = self.spec.trust_ratio
+        if trust_ratio is not None:
+            _check_trust_ratio(trust_ratio)
+            if ddp_shard and group is not None and comm_size(group) > 1:
+                raise ValueError("trust_ratio with ddp_shard is not supported: a sharded member holds only "
+                                 "slices of the segments its norms run over")
         self.device = torch.device(device)
         if self.device.type == "cuda":
             _lib.load(required=True)
@@ -104,6 +111,13 @@ class Trainer:
         self._clip_part = None          # grad_sumsq's per-block fp64 partials
         self._clip_host = [1.0, 0.0, 0, 0]   # the same four words on the CPU path
         self.set_grad_clip(grad_clip)
+        # layer-wise trust ratio (set_trust_ratio: LARS for an sgd job, LAMB
+        # for an adam job); None = off, nothing allocated or launched
+        self.trust_ratio: Optional[float] = None
+        self._tr = None                 # device (tiles, seg_first, partials, ratios) of lars_step / lamb_step
+        self._tr_host: Dict[str, tuple] = {}   # the last step's ratios on the CPU path
+        self._tr_stepped = False        # an optimizer step ran with the knob on since reset
+        self.set_trust_ratio(trust_ratio)
         # training dropout (set_dropout) and attention-probability dropout
         # (set_attn_dropout); None = off, and with both off nothing is
         # allocated or launched. They share the record and its one advance
@@ -303,6 +317,53 @@ class Trainer:
             st = [1.0, 0.0, st[2], st[3]]
         return {"last_scale": st[0], "last_norm": st[1], "nonfinite_steps": st[2], "clipped_steps": st[3]}
 
+    # ------------------------------------------------------------ trust ratio
+    def set_trust_ratio(self, v: Optional[float]) -> None:
+        """Layer-wise adaptive learning rates with trust coefficient ``v``
+        (ETA): an ``sgd`` job runs LARS, an ``adam`` job LAMB; ``None`` turns
+        it off. Every weight-decayed parameter gets its own ratio from the
+        fp64-accumulated L2 norms of its weights and of its scaled gradient
+        (LARS) or update direction (LAMB); biases and norm parameters keep
+        ratio 1. On the GPU the norms, the ratios and their use stay on the
+        device (lars_step / lamb_step, three launches, no host read or sync);
+        ``trust_ratios()`` reads them after a round. The tile tables and the
+        partials are allocated on first use and hold nothing that outlives a
+        step. A non-sharded gang needs no extra collective: after the
+        all-reduce every member holds the same gradient and computes the same
+        ratios."""
+        if v is not None:
+            v = _check_trust_ratio(v)
+            if self.ddp is not None and self.ddp.shard:
+                raise ValueError("trust_ratio with ddp_shard is not supported: a sharded member holds only "
+                                 "slices of the segments its norms run over")
+            if self.opt_dtype == "bf16":
+                raise ValueError("trust_ratio with opt_dtype='bf16' is not supported: LAMB's second pass would "
+                                 "take the weights from the rounded moments")
+            if self.device.type == "cuda" and self._tr is None:
+                A = self.arena
+                segs = [(p.offset, _padded(p.numel)) for p in A.decay_segments()]
+                tiles, first = trust_tile_table(segs, int(_lib.ops().trust_tile()))
+                self._tr = (tiles.to(self.device), first.to(self.device),
+                            torch.zeros(max(1, tiles.shape[0]) * 2, dtype=torch.float64, device=self.device),
+                            torch.zeros(max(1, len(segs)), 3, dtype=torch.float32, device=self.device))
+        if v != self.trust_ratio:
+            self._tr_stepped = False
+            self._tr_host = {}
+        self.trust_ratio = v
+
+    def trust_ratios(self) -> Dict[str, tuple]:
+        """``{param name: (ratio, w_norm, other_norm)}`` of the last optimizer
+        step for every weight-decayed parameter; ``other_norm`` is the norm
+        of the scaled gradient (LARS) or of the update direction (LAMB).
+        Empty when the knob is off or before the first step. A host read:
+        call after the round's synchronize."""
+        if self.trust_ratio is None or not self._tr_stepped:
+            return {}
+        if self.device.type != "cuda":
+            return dict(self._tr_host)
+        rec = self._tr[3].cpu().tolist()
+        return {p.name: tuple(rec[i]) for i, p in enumerate(self.arena.decay_segments())}
+
     def _opt_step(self):
         A = self.arena
         gscale = self.ddp.grad_scale if self.ddp is not None else 1.0
@@ -336,7 +397,18 @@ class Trainer:
             guard = self.model.err if self.uses_persist else None
             zf = A.n_store if Fx.STORE_GRAD else 0
             clip = self._clip_launch(gscale)
-            if self.opt_dtype == "bf16":
+            if self.trust_ratio is not None:
+                # (fp32 state only: set_trust_ratio rejects opt_dtype="bf16")
+                tiles, first, part, ratios = self._tr
+                if self.opt == "sgd":
+                    T.lars_step(A.master, A.grad, self.opt_state[0], A.shadow, self.lr, 0.9, self.spec.wd,
+                                self.trust_ratio, gscale, tiles, first, part, ratios, guard, zf, A.n_decay, clip)
+                else:
+                    T.lamb_step(A.master, A.grad, self.opt_state[0], self.opt_state[1], A.shadow, self.lr, 0.9, 0.98,
+                                1e-9, self.spec.wd, self.step_count, self.trust_ratio, gscale, tiles, first, part,
+                                ratios, guard, zf, A.n_decay, clip)
+                self._tr_stepped = True
+            elif self.opt_dtype == "bf16":
                 # bf16 moments, stochastically rounded: the draws are a pure
                 # function of (seed, step, arena index), nothing is stored
                 seed = int(self.seed) & 0xFFFFFFFF
@@ -372,6 +444,16 @@ class Trainer:
                     A.grad.zero_()
                     regions = []
                 st[0], st[1] = scale, norm
+            if self.trust_ratio is not None and regions:
+                # the device path in plain torch, one decayed parameter at a
+                # time; the no-decay tail below is the plain step with wd = 0
+                for p in A.decay_segments():
+                    lo, hi = p.offset, p.offset + _padded(p.numel)
+                    self._tr_host[p.name] = _cpu_trust_opt(self.opt, A.master[lo:hi], A.grad[lo:hi], self.opt_state,
+                                                           lo, hi, A.shadow[lo:hi], self.lr, self.spec.wd, gscale,
+                                                           self.step_count, self.trust_ratio)
+                self._tr_stepped = True
+                regions = regions[1:]
         # (the per-region device launches below are the sharded gang's, where
         # clipping is rejected: clip is None there)
         clip = None
@@ -705,6 +787,10 @@ class Trainer:
         if self._clip is not None:
             self._clip.zero_()
         self._clip_host = [1.0, 0.0, 0, 0]
+        if self._tr is not None:
+            self._tr[3].zero_()
+        self._tr_host = {}
+        self._tr_stepped = False
         if self.device.type == "cuda":
             self._ready = torch.cuda.Event()
             self._ready.record(torch.cuda.current_stream(self.device))
@@ -717,6 +803,8 @@ class Trainer:
             raise ValueError("grad_clip with ddp_shard is not supported")
         if self.opt_dtype == "bf16" and self.ddp_shard and group is not None and comm_size(group) > 1:
             raise ValueError("opt_dtype='bf16' with ddp_shard is not supported")
+        if self.trust_ratio is not None and self.ddp_shard and group is not None and comm_size(group) > 1:
+            raise ValueError("trust_ratio with ddp_shard is not supported")
         # sharded state survives only a re-created communicator over the SAME
         # rank set (same member positions); anything else needs consolidate()
         dirty = self.state_sharded
@@ -770,6 +858,41 @@ class Trainer:
         self._g_loss = None
         self.last_loss = None                    # may alias the graph's output
         self.arena.on_grad_ready = None
+
+
+def _check_trust_ratio(v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0 or v == float("inf"):
+        raise ValueError(f"trust_ratio must be a finite number > 0, got {v!r}")
+    return float(v)
+
+
+def _cpu_trust_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, eta):
+    """One decayed segment's LARS (``sgd``) / LAMB (``adam``) step in plain
+    torch, the formulas of optim.hip "layer-wise trust ratio" with fp64
+    norms. Returns (ratio, w_norm, other_norm)."""
+    gg = g * gscale
+    wn = float(w.double().norm())
+    if opt == "sgd":
+        xn = float(gg.double().norm())
+        ok = 0.0 < wn < float("inf") and 0.0 < xn < float("inf")
+        r = eta * wn / (xn + wd * wn) if ok else 1.0
+        m = state[0][lo:hi]
+        m.mul_(0.9).add_(float(torch.tensor(r, dtype=torch.float32)) * (gg + wd * w))
+        w.sub_(lr * m)
+    else:
+        m, v = state[0][lo:hi], state[1][lo:hi]
+        m.mul_(0.9).add_(0.1 * gg)
+        v.mul_(0.98).add_(0.02 * gg * gg)
+        mh = m / (1 - 0.9 ** step)
+        vh = v / (1 - 0.98 ** step)
+        u = mh / (vh.sqrt() + 1e-9) + wd * w
+        xn = float(u.double().norm())
+        ok = 0.0 < wn < float("inf") and 0.0 < xn < float("inf")
+        r = eta * wn / xn if ok else 1.0
+        w.sub_((lr * float(torch.tensor(r, dtype=torch.float32))) * u)
+    g.zero_()
+    wb.copy_(w.to(torch.bfloat16))
+    return (float(torch.tensor(r, dtype=torch.float32)), wn, xn)
 
 
 def _cpu_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, seed=None):

@@ -56,6 +56,10 @@ class ModelSpec:
     # "fp32" keep fp32 moments, "bf16" keeps them in bf16 with stochastic
     # rounding. No shipped model sets it
     opt_dtype: Optional[str] = None
+    # layer-wise trust coefficient of the job's recipe (Trainer.set_trust_ratio,
+    # --trust-ratio): LARS for an sgd model, LAMB for an adam model; None =
+    # off. No shipped model sets it
+    trust_ratio: Optional[float] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

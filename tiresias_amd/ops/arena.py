@@ -25,7 +25,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -81,6 +81,29 @@ class Param:
 
 def _padded(n: int) -> int:
     return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def trust_tile_table(segments: Sequence[Tuple[int, int]], tile: int):
+    """Tile table of the layer-wise trust-ratio optimizers (optim.hip
+    lars_step / lamb_step). ``segments``: (offset, padded length) of every
+    decayed parameter, in arena order; ``tile``: elements per tile
+    (``ops.trust_tile()``, a multiple of 64). Every segment is cut into tiles
+    of ``tile`` elements, the last one possibly short; no tile crosses a
+    segment. Returns two int32 CPU tensors: ``tiles`` [ntiles, 4] = (start,
+    length, segment, 0) and ``seg_first`` [nseg + 1], the first tile of every
+    segment followed by ntiles."""
+    if tile <= 0 or tile % _ALIGN:
+        raise ValueError(f"tile must be a positive multiple of {_ALIGN}, got {tile}")
+    rows, first = [], []
+    for s, (off, n) in enumerate(segments):
+        if off % _ALIGN or n % _ALIGN or n <= 0 or off + n >= 2 ** 31:
+            raise ValueError(f"segment {s}: ({off}, {n}) is not a padded extent below 2^31")
+        first.append(len(rows))
+        for a in range(0, n, tile):
+            rows.append((off + a, min(tile, n - a), s, 0))
+    first.append(len(rows))
+    tiles = torch.tensor(rows, dtype=torch.int32).reshape(-1, 4)
+    return tiles, torch.tensor(first, dtype=torch.int32)
 
 
 class Arena:
@@ -182,6 +205,12 @@ class Arena:
 
     def state_bytes(self) -> int:
         return self.numel * (4 + 2 + 4)
+
+    def decay_segments(self) -> List[Param]:
+        """The weight-decayed params in arena order: the segments
+        [offset, offset + padded(numel)) that tile [0, n_decay) and get a
+        layer-wise trust ratio (``trust_tile_table``)."""
+        return [p for p in self._order() if p.decay]
 
     def named(self):
         return {p.name: p for p in self.params}

@@ -10,7 +10,14 @@ of it (the difference is what clipping adds to a step).
 ``--bf16-state`` also times, per arena at the production variant / grid, the
 step with fp32 state against the step with bf16 state and Philox stochastic
 rounding (``*_step_bf16s``), interleaved, with the bytes each form moves per
-element (Adam 34 -> 26, SGD 26 -> 22)."""
+element (Adam 34 -> 26, SGD 26 -> 22).
+
+``--trust-ratio`` also times, per arena with the model's real segment layout,
+the plain step against the layer-wise trust-ratio step of the same build
+(``lars_step`` on the SGD arenas, ``lamb_step`` on the Adam arenas: segmented
+norms, finalize, apply), interleaved in one process, with the bytes each form
+moves per element (SGD 26 -> LARS 34, Adam 34 -> LAMB 46).
+``OPTIM_VARIANTS=3`` skips the variant sweep in front of it."""
 import json
 import os
 import sys
@@ -40,6 +47,9 @@ def main():
     bf16_rows = "--bf16-state" in sys.argv
     if bf16_rows:
         sys.argv.remove("--bf16-state")
+    trust_rows = "--trust-ratio" in sys.argv
+    if trust_rows:
+        sys.argv.remove("--trust-ratio")
     _lib.load(required=True)
     T = _lib.ops()
     dev = torch.device("cuda", 0)
@@ -120,6 +130,47 @@ def main():
                     print(json.dumps(r), flush=True)
                     out.append(r)
             del mb, vb
+        if trust_rows:
+            from tiresias_amd.models import make_model
+            from tiresias_amd.ops.arena import Arena, _padded, trust_tile_table
+
+            lay = Arena("cpu")                   # the model's real segment layout; nothing is materialized
+            make_model(name, lay)
+            lay.layout()
+            assert lay.numel == n, (name, lay.numel, n)
+            nd = lay.n_decay
+            segs = [(p.offset, _padded(p.numel)) for p in lay.decay_segments()]
+            tiles, first = trust_tile_table(segs, int(T.trust_tile()))
+            tiles, first = tiles.to(dev), first.to(dev)
+            part = torch.zeros(2 * tiles.shape[0], dtype=torch.float64, device=dev)
+            ratios = torch.zeros(len(segs), 3, device=dev)
+
+            def plain():
+                if opt == "sgd":
+                    T.sgd_step(w, g, m, wb, 0.1, 0.9, 1e-4, 1.0, False, True, None, 0, nd)
+                else:
+                    T.adam_step(w, g, m, v, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, 3, 1.0, True, None, 0, nd)
+
+            def trust():
+                if opt == "sgd":
+                    T.lars_step(w, g, m, wb, 0.1, 0.9, 1e-4, 1e-3, 1.0, tiles, first, part, ratios, None, 0, nd)
+                else:
+                    T.lamb_step(w, g, m, v, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, 3, 1.0, 1.0, tiles, first, part, ratios,
+                                None, 0, nd)
+
+            # bytes per element: the plain step, and the three passes (LARS:
+            # w g | w g mom -> w mom g wb; LAMB: w g m v -> m v g | w m v -> w wb)
+            per = {"sgd": (26, 34), "adam": (34, 46)}[opt]
+            for _ in range(3):                                                # three interleaved rounds
+                g.normal_()          # (the steps zero the gradient: refill, so no round times a zero one)
+                for kind, fn, bpe in (("plain", plain, per[0]), ("lars" if opt == "sgd" else "lamb", trust, per[1])):
+                    us = timeit(fn)
+                    r = dict(model=name, opt=opt, kind=kind, params=n, segments=len(segs), tiles=int(tiles.shape[0]),
+                             tile=int(T.trust_tile()), bytes_per_elem=bpe, us=round(us, 1),
+                             tb_per_s=round(bpe * n / us / 1e6, 2))
+                    print(json.dumps(r), flush=True)
+                    out.append(r)
+            del tiles, first, part, ratios
         del v
         del w, g, m, wb
         torch.cuda.empty_cache()
