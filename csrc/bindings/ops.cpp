@@ -1401,6 +1401,55 @@ void lamb_op(const Tensor& w, const Tensor& g, const Tensor& m, const Tensor& v,
                  guard_ptr(guard, w), (long)zero_from, nd, clip_ptr(clip, w));
 }
 int64_t trust_tile_op() { return tam::trust_tile(); }
+// Adafactor (adafactor.hip): params int32 [nparam][8], tiles int32 [ntiles][4],
+// tasks int32 [ntasks][4], state / fac float32 [nstate], partials float32,
+// tslots float64 [ntiles], urms float32 [nparam][2]. The kernels bound-check
+// every table record against these sizes
+void adafactor_op(const Tensor& w, const Tensor& g, const Tensor& state, const Tensor& fac, const Tensor& wb,
+                  double lr, double wd, int64_t step, double gscale, const Tensor& params, const Tensor& tiles,
+                  const Tensor& tasks, const Tensor& partials, const Tensor& tslots, const Tensor& urms,
+                  const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until, const optional<Tensor>& clip) {
+  const char* op = "tam.adafactor_step";
+  check_f32(w, "w"); check_contig(w, "w"); check_bf16(wb, "wb"); check_contig(wb, "wb");
+  check_f32(g, "g"); check_contig(g, "g");
+  const int64_t n = w.numel();
+  TORCH_CHECK(n > 0 && n % 64 == 0 && n < (1LL << 31) && wb.numel() == n && g.numel() == n &&
+                  wb.device() == w.device() && g.device() == w.device(), op,
+              ": numel % 64, below 2^31, and a gradient and a shadow of the same size on w's device");
+  TORCH_CHECK(((((uintptr_t)w.data_ptr()) | ((uintptr_t)g.data_ptr())) & 15) == 0 &&
+                  (((uintptr_t)wb.data_ptr()) & 7) == 0, op, ": w / g must be 16-B aligned, wb 8-B aligned");
+  for (const Tensor* t : {&state, &fac, &partials, &urms}) {
+    check_f32(*t, "state / fac / partials / urms"); check_contig(*t, "state / fac / partials / urms");
+    TORCH_CHECK(t->device() == w.device() && t->numel() < (1LL << 31), op,
+                ": state, fac, partials and urms must be float32 tensors below 2^31 on the parameters' device");
+  }
+  TORCH_CHECK(fac.numel() == state.numel(), op, ": fac must have the state's size");
+  TORCH_CHECK(step >= 1 && step <= 0x7fffffffLL, op, ": step must be a 1-based optimizer step, got ", step);
+  TORCH_CHECK(zero_from >= 0 && zero_from % 4 == 0 && (wd_until < 0 || (wd_until <= n && wd_until % 64 == 0)), op,
+              ": zero_from % 4, wd_until a multiple of 64 inside the arena");
+  for (const Tensor* t : {&params, &tiles, &tasks}) {
+    check_dev(*t, "tables"); check_contig(*t, "tables");
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->device() == w.device() && t->numel() >= 4 &&
+                    (((uintptr_t)t->data_ptr()) & 15) == 0, op,
+                ": params / tiles / tasks must be non-empty, 16-B aligned int32 tensors on the parameters' device");
+  }
+  TORCH_CHECK(params.numel() % 8 == 0 && tiles.numel() % 4 == 0 && tasks.numel() % 4 == 0, op,
+              ": params must be [nparam][8], tiles [ntiles][4], tasks [ntasks][4]");
+  const int64_t np = params.numel() / 8, nt = tiles.numel() / 4, nk = tasks.numel() / 4;
+  TORCH_CHECK(nt <= (1 << 24) && nk <= (1 << 24) && np <= nt, op, ": ", np, " parameters, ", nt, " tiles, ", nk,
+              " tasks");
+  check_dev(tslots, "tslots"); check_contig(tslots, "tslots");
+  TORCH_CHECK(tslots.scalar_type() == at::kDouble && tslots.device() == w.device() && tslots.numel() >= nt, op,
+              ": tslots must be float64 [ntiles] on the parameters' device");
+  TORCH_CHECK(urms.numel() >= 2 * np, op, ": urms holds ", urms.numel(), " floats, ", np, " parameters need ", 2 * np);
+  tam::adafactor_step(w.data_ptr<float>(), g.data_ptr<float>(), state.data_ptr<float>(), fac.data_ptr<float>(),
+                      bpm(wb), n, state.numel(), (float)lr, (float)wd, (int)step, (float)gscale,
+                      params.data_ptr<int>(), (int)np, tiles.data_ptr<int>(), (int)nt, tasks.data_ptr<int>(), (int)nk,
+                      partials.data_ptr<float>(), partials.numel(), tslots.data_ptr<double>(),
+                      urms.data_ptr<float>(), cur_stream(w), guard_ptr(guard, w), (long)zero_from, (long)wd_until,
+                      clip_ptr(clip, w));
+}
+std::vector<int64_t> adafactor_tile_op() { return {tam::adafactor_tile_rows(), tam::adafactor_tile_cols()}; }
 void lstm_guard_step_op(const Tensor& err) {
   TORCH_CHECK(err.is_cuda() && err.scalar_type() == at::kInt && err.numel() >= 2,
               "tam.lstm_guard_step: err must be an int32 [2] GPU tensor");
@@ -1670,6 +1719,8 @@ TORCH_LIBRARY(tam, m) {
   m.def("lars_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float eta, float gscale, Tensor tiles, Tensor seg_first, Tensor(e!) partials, Tensor(f!) ratios, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &lars_op);
   m.def("lamb_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float eta, float gscale, Tensor tiles, Tensor seg_first, Tensor(f!) partials, Tensor(g!) ratios, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &lamb_op);
   m.def("trust_tile() -> int", &trust_tile_op);
+  m.def("adafactor_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) state, Tensor(d!) fac, Tensor(e!) wb, float lr, float wd, int step, float gscale, Tensor params, Tensor tiles, Tensor tasks, Tensor(f!) partials, Tensor(g!) tslots, Tensor(h!) urms, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adafactor_op);
+  m.def("adafactor_tile() -> int[]", &adafactor_tile_op);
   m.def("lstm_guard_step(Tensor(a!) err) -> ()", &lstm_guard_step_op);
   m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_forward_op);
   m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_backward_op);

@@ -190,6 +190,20 @@ void lamb_step(float* w, float* g, float* m, float* v, bf16_t* wb, long n, float
                float wd, int step, float eta, float gscale, const int* tiles, int ntiles, const int* seg_first,
                int nseg, double* partials, float* ratios, hipStream_t s, const unsigned* guard = nullptr,
                long zero_from = 0, long wd_until = -1, const float* clip = nullptr);
+int optim_tile_grid(int ntiles);   // blocks of a tile-strided optimizer pass (the optim_grid cap)
+// Adafactor with factored second moments (adafactor.hip; contract, table
+// formats and the six passes are described there). state / fac float
+// [nstate]: every parameter's [Rv | Cv] slice and the step's rfac / cfac;
+// partials float [npart], tslots double [ntiles], urms float [nparam][2] =
+// {RMS(u), clip scale s} of the last step. step: the 1-based optimizer step.
+// guard / clip as in the plain steps: a skipped step only resets the gradient.
+int adafactor_tile_rows();
+int adafactor_tile_cols();
+void adafactor_step(float* w, float* g, float* state, float* fac, bf16_t* wb, long n, long nstate, float lr,
+                    float wd, int step, float gscale, const int* params, int nparam, const int* tiles, int ntiles,
+                    const int* tasks, int ntasks, float* partials, long npart, double* tslots, float* urms,
+                    hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+                    const float* clip = nullptr);
 
 // fused attention (bf16, head_dim 64): element (b, s, h, d) at b * *_bstride +
 // s * *_stride + 64 h + d (batch-major [B][S][H][64], or a time-major

@@ -861,6 +861,7 @@ static int tgrid(int ntiles) {
   const int cap = ogrid(1L << 40);
   return ntiles < cap ? (ntiles < 1 ? 1 : ntiles) : cap;
 }
+int optim_tile_grid(int ntiles) { return tgrid(ntiles); }   // (adafactor.hip)
 
 void lars_step(float* w, float* g, float* mom, bf16_t* wb, long n, float lr, float momentum, float wd, float eta,
                float gscale, const int* tiles, int ntiles, const int* seg_first, int nseg, double* partials,

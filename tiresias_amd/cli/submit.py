@@ -38,10 +38,12 @@ def main(argv=None) -> int:
                     help="dropout probability on the attention probabilities, inside the attention kernels "
                          "(0 <= p < 1, quantised to 1/256: 0.1 drops 26/256); models without attention "
                          "dropout ignore it")
-    ap.add_argument("--opt-dtype", choices=("fp32", "bf16"),
+    ap.add_argument("--opt-dtype", choices=("fp32", "bf16", "factored"),
                     help="format of the optimizer state: bf16 keeps the moments in bf16 with stochastic "
                          "rounding (4 B per parameter less for Adam, 2 B for SGD, resident and spilled); "
-                         "default fp32")
+                         "factored runs Adafactor on an Adam model (row and column means of the second "
+                         "moment, no first moment: the state shrinks to O(rows + cols) per weight matrix; "
+                         "not combined with --trust-ratio); default fp32")
     ap.add_argument("--trust-ratio", type=float, metavar="ETA",
                     help="layer-wise adaptive learning rates with trust coefficient ETA > 0: LARS for an SGD "
                          "model, LAMB for an Adam model; not combined with --opt-dtype bf16")

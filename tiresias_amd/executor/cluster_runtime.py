@@ -149,7 +149,7 @@ class ReplayJob:
     grad_clip: Optional[float] = None    # global-norm gradient clip of the job (None = off)
     dropout: Optional[float] = None      # training dropout of the job (None = off)
     attn_dropout: Optional[float] = None     # attention-probability dropout of the job (None = off)
-    opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" (None = fp32)
+    opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" / "factored" (None = fp32)
     trust_ratio: Optional[float] = None  # layer-wise trust coefficient of the job: LARS / LAMB (None = off)
 
 
@@ -588,8 +588,15 @@ class Controller:
                 raise ValueError(f"attn_dropout must be a number p with 0 <= p < 1 (quantised to 1/256), got {adrop!r}")
             adrop = float(adrop)
         odt = req.get("opt_dtype")
-        if odt is not None and (not isinstance(odt, str) or odt not in ("fp32", "bf16")):
-            raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', got {odt!r}")
+        if odt is not None and (not isinstance(odt, str) or odt not in ("fp32", "bf16", "factored")):
+            raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', or 'factored' for an adam model, got {odt!r}")
+        if odt == "factored":
+            from ..models import MODELS
+
+            if model in MODELS and MODELS[model].opt != "adam":
+                raise ValueError(f"opt_dtype 'factored' (Adafactor) needs an adam model, {model!r} is not one")
+            if self.ddp_shard and g > 1:
+                raise ValueError("opt_dtype 'factored' is not supported for a multi-GPU job under ddp_shard")
         eta = req.get("trust_ratio")
         if eta is not None:
             if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta > 0 or eta == float("inf"):
@@ -597,8 +604,8 @@ class Controller:
             eta = float(eta)
             if self.ddp_shard and g > 1:
                 raise ValueError("trust_ratio is not supported for a multi-GPU job under ddp_shard")
-            if odt == "bf16":
-                raise ValueError("trust_ratio is not supported with opt_dtype 'bf16'")
+            if odt in ("bf16", "factored"):
+                raise ValueError(f"trust_ratio is not supported with opt_dtype {odt!r}")
         return jid, model, g, iters, batch, clip, drop, adrop, odt, eta
 
     def status(self) -> dict:
@@ -902,10 +909,10 @@ class Worker:
     def _pool_key(act) -> tuple:
         """Warm-pool key of a start action: what fixes a trainer's buffers.
         The optimizer-state format does (bf16 state buffers cannot serve a
-        fp32-state job, nor the reverse), so a bf16-state job's key carries it;
+        fp32-state job, nor the reverse), so a bf16- or factored-state job's key carries it;
         the per-job setters (clip, dropouts, trust ratio) are not part of the key."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
-        return key + ("bf16",) if act.get("opt_dtype") == "bf16" else key
+        return key + (act["opt_dtype"],) if act.get("opt_dtype") in ("bf16", "factored") else key
 
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
@@ -923,7 +930,7 @@ class Worker:
         if free:
             # the key carries the state format; a pooled trainer of the other
             # format under it would run the wrong kernels silently
-            want_dt = "bf16" if act.get("opt_dtype") == "bf16" else "fp32"
+            want_dt = act.get("opt_dtype") or "fp32"
             if free[-1].opt_dtype != want_dt:
                 raise RuntimeError(f"warm pool {key}: a {free[-1].opt_dtype}-state trainer is pooled under the "
                                    f"key of a {want_dt}-state job")
@@ -1057,8 +1064,9 @@ class Worker:
         """HBM a new job of ``model`` needs, in the units the budget counts
         (Trainer.hbm_bytes: state + batch): the measured growth when one was
         last created here with the same optimizer-state format, else 1.5x its
-        optimizer-inclusive state (bf16 moments priced at 2 B each)."""
-        nk = (model, "bf16") if opt_dtype == "bf16" else model
+        optimizer-inclusive state (bf16 moments priced at 2 B each, factored
+        state at its row and column means)."""
+        nk = (model, opt_dtype) if opt_dtype in ("bf16", "factored") else model
         if nk in self._need:
             return self._need[nk]
         from ..profiler.skew import model_profile
@@ -1238,7 +1246,8 @@ class Worker:
                         grown = torch.cuda.memory_allocated(self.device) - before
                         if grown > 0:      # a newly built trainer (not a warm-pool reuse)
                             # what _resident_bytes will count for it (state + batch)
-                            nk = (a["model"], "bf16") if a.get("opt_dtype") == "bf16" else a["model"]
+                            odt = a.get("opt_dtype")
+                            nk = (a["model"], odt) if odt in ("bf16", "factored") else a["model"]
                             self._need[nk] = max(self._need.get(nk, 0.0), float(grown))
             elif src == "resident":
                 t = self.trainers.get(a["job"])

@@ -17,7 +17,7 @@ import torch
 from ..models import MODELS, make_model, samples_per_batch, synthetic_batch
 from ..ops import _lib
 from ..ops import functional as Fx
-from ..ops.arena import Arena, _padded, trust_tile_table
+from ..ops.arena import Arena, _padded, adafactor_tables, factored_shape, trust_tile_table
 from ..parallel.ddp import GradBucketer
 from ..parallel.gang import comm_rank, comm_size
 
@@ -34,12 +34,23 @@ class Trainer:
         self.spec = MODELS[model]
         if opt_dtype is None:
             opt_dtype = self.spec.opt_dtype
-        if opt_dtype not in (None, "fp32", "bf16"):
-            raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', got {opt_dtype!r}")
-        # format of the optimizer state (README "bf16 optimizer state"). It
-        # fixes the buffer types, so it is set at construction (and is part of
-        # the worker's warm-pool key), not by a per-job setter
-        self.opt_dtype = "bf16" if opt_dtype == "bf16" else "fp32"
+        if opt_dtype not in (None, "fp32", "bf16", "factored"):
+            raise ValueError(f"opt_dtype must be 'fp32', 'bf16' or 'factored', got {opt_dtype!r}")
+        # format of the optimizer state (README "bf16 optimizer state",
+        # "Factored optimizer state"). It fixes the buffer types, so it is set
+        # at construction (and is part of the worker's warm-pool key), not by
+        # a per-job setter
+        self.opt_dtype = opt_dtype or "fp32"
+        if self.opt_dtype == "factored":
+            if self.spec.opt != "adam":
+                raise ValueError(f"opt_dtype='factored' is Adafactor, which replaces Adam: {model!r} is an "
+                                 f"{self.spec.opt!r} model")
+            if ddp_shard and group is not None and comm_size(group) > 1:
+                raise ValueError("opt_dtype='factored' with ddp_shard is not supported: a sharded member holds "
+                                 "only slices of the rows its row and column means run over")
+            if trust_ratio is not None or self.spec.trust_ratio is not None:
+                raise ValueError("opt_dtype='factored' with trust_ratio is not supported: LAMB's ratio is "
+                                 "defined over Adam's update")
         if self.opt_dtype == "bf16" and ddp_shard and group is not None and comm_size(group) > 1:
             raise ValueError("opt_dtype='bf16' with ddp_shard is not supported: the sharded gang's slice "
                              "launches and state all-gather are fp32-state only")
@@ -71,7 +82,16 @@ class Trainer:
         self.opt = self.spec.opt
         self.lr = lr if lr is not None else self.spec.lr
         sdt = torch.bfloat16 if self.opt_dtype == "bf16" else torch.float32
-        self.opt_state = [torch.zeros(n, dtype=sdt, device=self.device) for _ in range(1 if self.opt == "sgd" else 2)]
+        self._af = None                 # device tables and scratch of adafactor_step
+        self._af_host: Dict[str, tuple] = {}   # the last step's (rms, scale) on the CPU path
+        self._af_stepped = False
+        if self.opt_dtype == "factored":
+            # ONE fp32 tensor: every parameter's R row means and C column
+            # means, in arena order, each slice padded to 64
+            self._af_alloc()
+        else:
+            self.opt_state = [torch.zeros(n, dtype=sdt, device=self.device)
+                              for _ in range(1 if self.opt == "sgd" else 2)]
         self.step_count = 0
         self.data = synthetic_batch(model, self.batch, self.device,
                                     seed=seed if data_seed is None else data_seed)
@@ -339,6 +359,9 @@ class Trainer:
             if self.opt_dtype == "bf16":
                 raise ValueError("trust_ratio with opt_dtype='bf16' is not supported: LAMB's second pass would "
                                  "take the weights from the rounded moments")
+            if self.opt_dtype == "factored":
+                raise ValueError("trust_ratio with opt_dtype='factored' is not supported: LAMB's ratio is "
+                                 "defined over Adam's update")
             if self.device.type == "cuda" and self._tr is None:
                 A = self.arena
                 segs = [(p.offset, _padded(p.numel)) for p in A.decay_segments()]
@@ -363,6 +386,35 @@ class Trainer:
             return dict(self._tr_host)
         rec = self._tr[3].cpu().tolist()
         return {p.name: tuple(rec[i]) for i, p in enumerate(self.arena.decay_segments())}
+
+    # ------------------------------------------------------------ factored state
+    def _af_alloc(self) -> None:
+        A = self.arena
+        order = A._order()
+        tile = [int(v) for v in _lib.ops().adafactor_tile()] if self.device.type == "cuda" else [32, 256]
+        params, tiles, tasks, nstate, npart = adafactor_tables([(p.offset, p.shape) for p in order], *tile)
+        self.opt_state = [torch.zeros(nstate, dtype=torch.float32, device=self.device)]
+        # name -> (state offset, R, C)
+        self._af_slices = {p.name: (int(r[3]), int(r[1]), int(r[2])) for p, r in zip(order, params.tolist())}
+        if self.device.type == "cuda":
+            dev = self.device
+            self._af = (params.to(dev), tiles.to(dev), tasks.to(dev),
+                        torch.zeros(nstate, dtype=torch.float32, device=dev),              # rfac / cfac
+                        torch.zeros(max(1, npart), dtype=torch.float32, device=dev),       # row / column partials
+                        torch.zeros(tiles.shape[0], dtype=torch.float64, device=dev),      # sum of u^2 per tile
+                        torch.zeros(len(order), 2, dtype=torch.float32, device=dev))       # {RMS(u), s}
+
+    def update_rms(self) -> Dict[str, tuple]:
+        """``{param name: (rms, scale)}`` of the last Adafactor step: the RMS
+        of every parameter's update direction and the clip ``1 / max(1,
+        rms)`` it was applied with. Empty unless ``opt_dtype="factored"`` and a
+        step has run. A host read: call after the round's synchronize."""
+        if self.opt_dtype != "factored" or not self._af_stepped:
+            return {}
+        if self.device.type != "cuda":
+            return dict(self._af_host)
+        rec = self._af[6].cpu().tolist()
+        return {p.name: tuple(rec[i]) for i, p in enumerate(self.arena._order())}
 
     def _opt_step(self):
         A = self.arena
@@ -397,7 +449,14 @@ class Trainer:
             guard = self.model.err if self.uses_persist else None
             zf = A.n_store if Fx.STORE_GRAD else 0
             clip = self._clip_launch(gscale)
-            if self.trust_ratio is not None:
+            if self.opt_dtype == "factored":
+                # Adafactor: one call over the arena, decay region and tail
+                params, tiles, tasks, fac, part, slots, urms = self._af
+                T.adafactor_step(A.master, A.grad, self.opt_state[0], fac, A.shadow, self.lr, self.spec.wd,
+                                 self.step_count, gscale, params, tiles, tasks, part, slots, urms, guard, zf,
+                                 A.n_decay, clip)
+                self._af_stepped = True
+            elif self.trust_ratio is not None:
                 # (fp32 state only: set_trust_ratio rejects opt_dtype="bf16")
                 tiles, first, part, ratios = self._tr
                 if self.opt == "sgd":
@@ -444,6 +503,19 @@ class Trainer:
                     A.grad.zero_()
                     regions = []
                 st[0], st[1] = scale, norm
+            if self.opt_dtype == "factored" and regions:
+                # the device path in plain torch, one parameter at a time
+                for p in A._order():
+                    lo, hi = p.offset, p.offset + p.numel
+                    so, R, C = self._af_slices[p.name]
+                    self._af_host[p.name] = _cpu_adafactor(
+                        A.master[lo:hi].view(R, C), A.grad[lo:hi].view(R, C), self.opt_state[0][so:so + R],
+                        self.opt_state[0][so + R:so + R + C], self.lr, self.spec.wd if p.decay else 0.0, gscale,
+                        self.step_count)
+                A.grad.zero_()
+                A.shadow.copy_(A.master.to(torch.bfloat16))
+                self._af_stepped = True
+                regions = []
             if self.trust_ratio is not None and regions:
                 # the device path in plain torch, one decayed parameter at a
                 # time; the no-decay tail below is the plain step with wd = 0
@@ -791,6 +863,10 @@ class Trainer:
             self._tr[3].zero_()
         self._tr_host = {}
         self._tr_stepped = False
+        if self._af is not None:
+            self._af[6].zero_()
+        self._af_host = {}
+        self._af_stepped = False
         if self.device.type == "cuda":
             self._ready = torch.cuda.Event()
             self._ready.record(torch.cuda.current_stream(self.device))
@@ -805,6 +881,8 @@ class Trainer:
             raise ValueError("opt_dtype='bf16' with ddp_shard is not supported")
         if self.trust_ratio is not None and self.ddp_shard and group is not None and comm_size(group) > 1:
             raise ValueError("trust_ratio with ddp_shard is not supported")
+        if self.opt_dtype == "factored" and self.ddp_shard and group is not None and comm_size(group) > 1:
+            raise ValueError("opt_dtype='factored' with ddp_shard is not supported")
         # sharded state survives only a re-created communicator over the SAME
         # rank set (same member positions); anything else needs consolidate()
         dirty = self.state_sharded
@@ -893,6 +971,25 @@ def _cpu_trust_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, eta):
     g.zero_()
     wb.copy_(w.to(torch.bfloat16))
     return (float(torch.tensor(r, dtype=torch.float32)), wn, xn)
+
+
+def _cpu_adafactor(w, g, rv, cv, lr, wd, gscale, step):
+    """One parameter's Adafactor step in plain torch on its R x C views, the
+    formulas of adafactor.hip; ``rv`` / ``cv`` are its row / column means in
+    the state. Returns (rms, scale). The caller resets the gradient and
+    rebuilds the shadow."""
+    b2 = 1.0 - float(step) ** -0.8
+    gg = g * gscale
+    sq = gg.double() * gg.double() + 1e-30
+    rv.mul_(b2).add_(((1.0 - b2) * sq.mean(dim=1)).float())
+    cv.mul_(b2).add_(((1.0 - b2) * sq.mean(dim=0)).float())
+    rfac = (rv.double() / rv.double().mean()).rsqrt().float()
+    cfac = cv.double().rsqrt().float()
+    u = gg * rfac[:, None] * cfac[None, :]
+    rms = float(u.double().pow(2).mean().sqrt())
+    s = float(torch.tensor(1.0 / max(1.0, rms), dtype=torch.float32))
+    w.sub_(lr * (s * u + wd * w))
+    return (float(torch.tensor(rms, dtype=torch.float32)), s)
 
 
 def _cpu_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, seed=None):

@@ -106,6 +106,51 @@ def trust_tile_table(segments: Sequence[Tuple[int, int]], tile: int):
     return tiles, torch.tensor(first, dtype=torch.int32)
 
 
+def factored_shape(shape: Sequence[int]) -> Tuple[int, int]:
+    """(R, C) of a parameter under Adafactor (adafactor.hip): ``shape[0]`` x
+    the rest when that has at least two rows and a column count the 16-B
+    accesses can take, else 1 x numel (biases, norm parameters, odd shapes),
+    whose factored second moment IS the plain one."""
+    n = int(math.prod(shape))
+    if len(shape) >= 2 and shape[0] >= 2 and (n // shape[0]) % 4 == 0:
+        return int(shape[0]), n // int(shape[0])
+    return 1, n
+
+
+def factored_state_numel(shapes: Sequence[Sequence[int]]) -> int:
+    """Elements of the factored optimizer state: every parameter's R row
+    means and C column means, the slice padded to 64."""
+    return sum(_padded(sum(factored_shape(s))) for s in shapes)
+
+
+def adafactor_tables(params: Sequence[Tuple[int, Sequence[int]]], tile_rows: int, tile_cols: int):
+    """Tables of ``ops.adafactor_step`` (formats in adafactor.hip).
+    ``params``: (arena offset, shape) of every parameter in arena order;
+    ``tile_rows`` x ``tile_cols``: ``ops.adafactor_tile()``. Every parameter's
+    R x C matrix is cut into tiles row block by row block; its rows and its
+    columns are cut into tasks of at most 256 entries. Returns int32 CPU
+    tensors ``params`` [n, 8], ``tiles`` [ntiles, 4], ``tasks`` [ntasks, 4]
+    and the element counts ``nstate``, ``npart`` of the state / partial
+    buffers."""
+    prow, trow, krow = [], [], []
+    soff = poff = 0
+    for i, (off, shape) in enumerate(params):
+        R, C = factored_shape(shape)
+        if off % _ALIGN or off + _padded(R * C) >= 2 ** 31:
+            raise ValueError(f"parameter {i}: offset {off} is not a padded extent below 2^31")
+        ntr, ntc = -(-R // tile_rows), -(-C // tile_cols)
+        prow.append((off, R, C, soff, poff, len(trow), ntr * ntc, 0))
+        for r0 in range(0, R, tile_rows):
+            for c0 in range(0, C, tile_cols):
+                trow.append((off + r0 * C + c0, min(tile_rows, R - r0), min(tile_cols, C - c0), i))
+        for kind, n in ((0, R), (1, C)):
+            krow += [(i, kind, a, min(256, n - a)) for a in range(0, n, 256)]
+        soff += _padded(R + C)
+        poff += ntc * R + ntr * C
+    t = lambda rows, k: torch.tensor(rows, dtype=torch.int32).reshape(-1, k)   # noqa: E731
+    return t(prow, 8), t(trow, 4), t(krow, 4), soff, poff
+
+
 class Arena:
     def __init__(self, device: torch.device | str = "cpu", seed: int = 0):
         self.device = torch.device(device)

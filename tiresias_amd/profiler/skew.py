@@ -38,6 +38,7 @@ class ModelProfile:
     tensors: List[float]          # MB per gradient tensor (fp32)
     total_mb: float
     largest_mb: float
+    factored: int = 0             # elements of the factored optimizer state (0: shapes unknown)
 
     @property
     def skew(self) -> float:
@@ -46,6 +47,10 @@ class ModelProfile:
     def state_bytes(self, opt: str = "sgd", opt_dtype: Optional[str] = None) -> int:
         # master fp32 + bf16 shadow + optimizer state (1 or 2 buffers, fp32
         # or, for a job with opt_dtype="bf16", bf16)
+        if opt_dtype == "factored" and self.factored:
+            # Adafactor (an adam model's opt_dtype="factored"): row and column
+            # means only, no first moment
+            return self.params * (4 + 2) + self.factored * 4
         per = 2 if opt_dtype == "bf16" else 4
         return self.params * (4 + 2 + (1 if opt == "sgd" else 2) * per)
 
@@ -58,6 +63,7 @@ class _ShapeArena:
 
         self.device = torch.device("cpu")
         self.shapes = []
+        self.full_shapes = []
         self.token = None
 
     def add(self, name, shape, init="normal", std=0.02, decay=True, fp32_compute=False, store_grad=False):
@@ -69,6 +75,7 @@ class _ShapeArena:
             n *= int(s)
         p.numel = n
         self.shapes.append((name, n))
+        self.full_shapes.append(tuple(int(s) for s in shape))
         return p
 
 
@@ -80,7 +87,10 @@ def model_profile(name: str) -> ModelProfile:
         ar = _ShapeArena()
         make_model(name, ar)
         sizes = [n * 4 / 2 ** 20 for _, n in ar.shapes]
-        return ModelProfile(name, sum(n for _, n in ar.shapes), sizes, sum(sizes), max(sizes))
+        from ..ops.arena import factored_state_numel
+
+        return ModelProfile(name, sum(n for _, n in ar.shapes), sizes, sum(sizes), max(sizes),
+                            factored_state_numel(ar.full_shapes))
     if name in LEGACY_PROFILES:
         k, tot, big = LEGACY_PROFILES[name]
         rest = (tot - big) / max(1, k - 1)

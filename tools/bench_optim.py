@@ -17,7 +17,14 @@ the plain step against the layer-wise trust-ratio step of the same build
 (``lars_step`` on the SGD arenas, ``lamb_step`` on the Adam arenas: segmented
 norms, finalize, apply), interleaved in one process, with the bytes each form
 moves per element (SGD 26 -> LARS 34, Adam 34 -> LAMB 46).
-``OPTIM_VARIANTS=3`` skips the variant sweep in front of it."""
+``OPTIM_VARIANTS=3`` skips the variant sweep in front of it.
+
+``--factored`` also times, on the Adam arenas with the model's real parameter
+shapes, ``adam_step`` against ``adafactor_step`` (adafactor.hip: six launches
+over the arena), interleaved in one process, with the bytes each moves per
+element (Adam 34, Adafactor 26: three reads of g, w read and written, shadow,
+gradient reset) and the optimizer-state bytes of each. ``OPTIM_MODELS=a,b``
+restricts every mode to those arenas."""
 import json
 import os
 import sys
@@ -50,6 +57,10 @@ def main():
     trust_rows = "--trust-ratio" in sys.argv
     if trust_rows:
         sys.argv.remove("--trust-ratio")
+    factored_rows = "--factored" in sys.argv
+    if factored_rows:
+        sys.argv.remove("--factored")
+    only = [m for m in os.environ.get("OPTIM_MODELS", "").split(",") if m]
     _lib.load(required=True)
     T = _lib.ops()
     dev = torch.device("cuda", 0)
@@ -58,6 +69,8 @@ def main():
     grids = [int(v) for v in os.environ.get("OPTIM_GRIDS", "0").split(",")]
     for name, n, opt in [("vgg16", 138360448, "sgd"), ("resnet50", 25572736, "sgd"),
                          ("gnmt", 226561280, "adam"), ("transformer", 60524544, "adam")]:
+        if only and name not in only:
+            continue
         w = torch.randn(n, device=dev); g = torch.randn(n, device=dev)
         m = torch.zeros(n, device=dev); wb = torch.empty(n, device=dev, dtype=torch.bfloat16)
         v = torch.zeros(n, device=dev) if opt == "adam" else None
@@ -171,6 +184,42 @@ def main():
                     print(json.dumps(r), flush=True)
                     out.append(r)
             del tiles, first, part, ratios
+        if factored_rows and opt == "adam":
+            from tiresias_amd.models import make_model
+            from tiresias_amd.ops.arena import Arena, adafactor_tables
+
+            lay = Arena("cpu")                   # the model's real parameter shapes; nothing is materialized
+            make_model(name, lay)
+            order = lay.layout()
+            assert lay.numel == n, (name, lay.numel, n)
+            nd = lay.n_decay
+            tabs = adafactor_tables([(p.offset, p.shape) for p in order], *[int(x) for x in T.adafactor_tile()])
+            params, tiles, tasks = (t.to(dev) for t in tabs[:3])
+            nstate, npart = tabs[3:]
+            state, fac = torch.zeros(nstate, device=dev), torch.zeros(nstate, device=dev)
+            part = torch.zeros(npart, device=dev)
+            slots = torch.zeros(tiles.shape[0], dtype=torch.float64, device=dev)
+            urms = torch.zeros(len(order), 2, device=dev)
+
+            def adam():
+                T.adam_step(w, g, m, v, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, 3, 1.0, True, None, 0, nd)
+
+            def adafactor():
+                T.adafactor_step(w, g, state, fac, wb, 1e-3, 0.01, 3, 1.0, params, tiles, tasks, part, slots, urms,
+                                 None, 0, nd)
+
+            for grid in grids * 3:                                            # three interleaved rounds
+                T.optim_grid(grid)
+                g.normal_()          # (the steps zero the gradient: refill, so no round times a zero one)
+                for kind, fn, bpe, sb in (("adam", adam, 34, 8 * n), ("adafactor", adafactor, 26, 4 * nstate)):
+                    us = timeit(fn)
+                    r = dict(model=name, opt=opt, kind=kind, grid=grid, params=n, tensors=len(order),
+                             tiles=int(tiles.shape[0]), state_bytes=sb, bytes_per_elem=bpe, us=round(us, 1),
+                             tb_per_s=round(bpe * n / us / 1e6, 2))
+                    print(json.dumps(r), flush=True)
+                    out.append(r)
+            T.optim_grid(0)
+            del params, tiles, tasks, state, fac, part, slots, urms
         del v
         del w, g, m, wb
         torch.cuda.empty_cache()
