@@ -875,6 +875,85 @@ void bn_backward_op(const Tensor& dy, const optional<Tensor>& y, const Tensor& x
                    sp, sums_ready ? 1 : 0, has_mask ? ymask->data_ptr<uint8_t>() : nullptr, cur_stream(x));
 }
 
+// GroupNorm: x [N, ..., C] (NHWC), groups G; returns P = pixels per sample.
+// The shapes the kernels serve are checked here: nothing else falls back
+static int64_t gn_shape(const Tensor& x, int64_t G, const char* op) {
+  check_bf16(x, "x"); check_contig(x, "x");
+  TORCH_CHECK(x.dim() >= 2 && x.numel() > 0, op, ": x must be [N, ..., C]");
+  const int64_t C = x.size(-1), N = x.size(0);
+  TORCH_CHECK(C % 8 == 0 && C <= 2048, op, ": C must be a multiple of 8 and <= 2048, got ", C);
+  TORCH_CHECK(G >= 1 && C % G == 0, op, ": groups must divide C (C = ", C, ", groups = ", G, ")");
+  const int64_t Cg = C / G;
+  TORCH_CHECK(Cg >= 2 && Cg <= 256 && (Cg & (Cg - 1)) == 0, op,
+              ": channels per group must be a power of two in [2, 256], got ", Cg);
+  const int64_t P = x.numel() / (N * C);
+  TORCH_CHECK(N <= 65535 && P * C < (int64_t(1) << 31), op, ": N <= 65535 and H*W*C < 2^31");
+  return P;
+}
+static void gn_like(const Tensor& t, const Tensor& x, const char* name, const char* op) {
+  check_bf16(t, name); check_contig(t, name);
+  TORCH_CHECK(t.numel() == x.numel() && t.device() == x.device(), op, ": ", name, " must match x");
+}
+static void gn_vec(const Tensor& t, int64_t n, const Tensor& x, const char* name, const char* op) {
+  check_f32(t, name);
+  TORCH_CHECK(t.is_contiguous() && t.numel() == n && t.device() == x.device(), op, ": ", name, " must be fp32 [", n, "]");
+}
+
+void groupnorm_forward_op(const Tensor& x, const optional<Tensor>& res, const Tensor& y, const Tensor& gamma,
+                          const Tensor& beta, const Tensor& mean, const Tensor& rstd, int64_t groups, double eps,
+                          bool relu) {
+  const char* op = "tam.groupnorm_forward";
+  const int64_t P = gn_shape(x, groups, op), C = x.size(-1), N = x.size(0);
+  gn_like(y, x, "y", op);
+  gn_vec(gamma, C, x, "gamma", op); gn_vec(beta, C, x, "beta", op);
+  gn_vec(mean, N * groups, x, "mean", op); gn_vec(rstd, N * groups, x, "rstd", op);
+  if (res.has_value() && res->defined()) gn_like(*res, x, "res", op);
+  Tensor ws = at::empty({N * tam::gn_tiles((int)P) * groups * 2}, x.options().dtype(at::kFloat));
+  tam::gn_forward(bp(x), opt_ptr<const tam::bf16_t>(res), bpm(y), (int)N, (int)P, (int)C, (int)groups, (float)eps,
+                  gamma.data_ptr<float>(), beta.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                  relu, ws.data_ptr<float>(), cur_stream(x));
+}
+
+// cpart: fp32, >= N * gn_tiles(P) * 2C, receives the per-block partial rows
+// (sum dy' x^ | sum dy'); returns their count. With dgamma / dbeta the column
+// reduce runs here; without, the caller runs (or defers) col_reduce_acc
+int64_t groupnorm_backward_op(const Tensor& dy, const optional<Tensor>& y, const Tensor& x, const Tensor& mean,
+                              const Tensor& rstd, const Tensor& gamma, const Tensor& dx,
+                              const optional<Tensor>& dres, const Tensor& cpart, const optional<Tensor>& dgamma,
+                              const optional<Tensor>& dbeta, int64_t groups, bool relu,
+                              const optional<Tensor>& addend) {
+  const char* op = "tam.groupnorm_backward";
+  const int64_t P = gn_shape(x, groups, op), C = x.size(-1), N = x.size(0);
+  gn_like(dy, x, "dy", op); gn_like(dx, x, "dx", op);
+  gn_vec(gamma, C, x, "gamma", op);
+  gn_vec(mean, N * groups, x, "mean", op); gn_vec(rstd, N * groups, x, "rstd", op);
+  const bool has_y = y.has_value() && y->defined();
+  TORCH_CHECK(!relu || has_y, op, ": relu needs y");
+  if (has_y) gn_like(*y, x, "y", op);
+  if (dres.has_value() && dres->defined()) gn_like(*dres, x, "dres", op);
+  if (addend.has_value() && addend->defined()) gn_like(*addend, x, "addend", op);
+  const int64_t T = tam::gn_tiles((int)P);
+  check_f32(cpart, "cpart");
+  TORCH_CHECK(cpart.is_contiguous() && cpart.numel() >= N * T * 2 * C && cpart.device() == x.device(), op,
+              ": cpart must hold N * tiles * 2C floats");
+  const bool fin = dgamma.has_value() && dgamma->defined();
+  TORCH_CHECK(fin == (dbeta.has_value() && dbeta->defined()), op, ": dgamma and dbeta go together");
+  if (fin) { gn_vec(*dgamma, C, x, "dgamma", op); gn_vec(*dbeta, C, x, "dbeta", op); }
+  Tensor ws = at::empty({(N * T + N) * groups * 2}, x.options().dtype(at::kFloat));
+  const int rows = tam::gn_backward(bp(dy), opt_ptr<const tam::bf16_t>(addend), relu ? bp(*y) : nullptr, bp(x),
+                                    mean.data_ptr<float>(), rstd.data_ptr<float>(), gamma.data_ptr<float>(), (int)N,
+                                    (int)P, (int)C, (int)groups, relu, bpm(dx), opt_ptr<tam::bf16_t>(dres),
+                                    cpart.data_ptr<float>(), ws.data_ptr<float>(), cur_stream(x));
+  if (fin)
+    tam::col_reduce_acc(cpart.data_ptr<float>(), rows, (int)(2 * C), dgamma->data_ptr<float>(),
+                        dbeta->data_ptr<float>(), (int)C, cur_stream(x));
+  return rows;
+}
+void gn_policy_op(int64_t p) { tam::gn_policy((int)p); }
+bool gn_resident_fits_op(int64_t P, int64_t C, int64_t groups, bool backward) {
+  return tam::gn_resident_fits((int)P, (int)C, (int)groups, backward ? 1 : 0);
+}
+
 // the dropout arguments of the LN ops / dropout_apply: rec (optional int32
 // [4] {seed, stream, step, 0} on the data's device), site, thr = round(p *
 // 65536) in (0, 65536), scale = 65536 / (65536 - thr); no rec = no dropout
@@ -1666,6 +1745,10 @@ TORCH_LIBRARY(tam, m) {
   m.def("ln_backward_split(Tensor dy, Tensor x, Tensor g, Tensor mean, Tensor rstd, Tensor(a!) dx, Tensor(b!) ws, Tensor? addend=None, Tensor(c!)? dr=None, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> int", &ln_backward_split_op);
   m.def("dropout_apply(Tensor x, Tensor(a!) y, Tensor rec, int site, int thr, float scale) -> ()", &dropout_apply_op);
   m.def("dropout_advance(Tensor(a!) rec) -> ()", &dropout_advance_op);
+  m.def("groupnorm_forward(Tensor x, Tensor? res, Tensor(a!) y, Tensor gamma, Tensor beta, Tensor(b!) mean, Tensor(c!) rstd, int groups, float eps, bool relu) -> ()", &groupnorm_forward_op);
+  m.def("groupnorm_backward(Tensor dy, Tensor? y, Tensor x, Tensor mean, Tensor rstd, Tensor gamma, Tensor(a!) dx, Tensor(b!)? dres, Tensor(c!) cpart, Tensor(d!)? dgamma, Tensor(e!)? dbeta, int groups, bool relu, Tensor? addend=None) -> int", &groupnorm_backward_op);
+  m.def("gn_policy(int policy) -> ()", &gn_policy_op);
+  m.def("gn_resident_fits(int P, int C, int groups, bool backward) -> bool", &gn_resident_fits_op);
   m.def("col_reduce_acc(Tensor part, int nblk, int W, Tensor(a!) out0, Tensor(b!) out1, int split) -> ()", &col_reduce_acc_op);
   m.def("col_reduce_acc_batch(Tensor[] parts, int[] nblk, Tensor(a!)[] out0, Tensor(b!)[] out1) -> ()", &col_reduce_acc_batch_op);
   m.def("maxpool_forward(Tensor x, Tensor(a!) y, Tensor(b!) idx, int R, int S, int stride, int pad) -> ()", &maxpool_forward_op);

@@ -53,6 +53,27 @@ void bn_backward(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const 
                  bf16_t* dres, float* dgamma, float* dbeta, double* sums, int sums_ready,
                  const uint8_t* ymask, hipStream_t s);
 
+// GroupNorm (group_norm.hip): x, res, y, dy, addend, dx, dres bf16 [N][P][C]
+// (NHWC, P = H * W), gamma / beta fp32 [C], mean / rstd fp32 [N][G]; C % 8 ==
+// 0, C <= 2048, Cg = C / G a power of two in [2, 256] (checked by the caller).
+// Two routes picked per (P, C, G): resident (one launch, the sample's slab
+// staged in LDS) and tiled (GN_TILE-pixel tiles, three passes).
+constexpr int GN_TILE = 256;
+inline int gn_tiles(int P) { return (P + GN_TILE - 1) / GN_TILE; }
+void gn_policy(int p);   // 0 auto, 1 tiled, 2 resident wherever its tile fits (A/B, tests)
+bool gn_resident_fits(int P, int C, int G, int backward);   // the resident tile(s) fit this device's LDS
+// y = relu?((x - mean_{n,g}) * rstd_{n,g} * gamma + beta (+ res)); ws: N * gn_tiles(P) * G * 2 floats
+void gn_forward(const bf16_t* x, const bf16_t* res, bf16_t* y, int N, int P, int C, int G, float eps,
+                const float* gamma, const float* beta, float* mean, float* rstd, int relu, float* ws,
+                hipStream_t s);
+// dy' = (dy + addend) masked by y > 0 when relu; dres (optional) = dy'; dx.
+// cpart: N * gn_tiles(P) partial rows [2C] (sum dy' x^ | sum dy'), the
+// returned count of which is written -- col_reduce_acc finishes dgamma | dbeta.
+// ws: (N * gn_tiles(P) + N) * G * 2 floats
+int gn_backward(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const bf16_t* x, const float* mean,
+                const float* rstd, const float* gamma, int N, int P, int C, int G, int relu, bf16_t* dx,
+                bf16_t* dres, float* cpart, float* ws, hipStream_t s);
+
 // LayerNorm over last dim D (D % 8 == 0, D <= 2048)
 // addend (optional): LN of (x + addend), the bf16 sum also stored to sum_out
 // (a residual add fused into the next pre-LN)

@@ -22,6 +22,10 @@ OBJ = ROOT / "build" / "obj"
 PKG = ROOT / "tiresias_amd"
 LIB = PKG / "_C.so"
 ARCH = os.environ.get("TAM_OFFLOAD_ARCH", "gfx950")
+# kernels compiled without the packed fp32 VALU forms (v_pk_add/mul/fma_f32),
+# kept to plain fp32 arithmetic
+_NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+NO_PACKED_FP32 = {"group_norm.hip": _NO_PK}
 
 
 def _hipcc() -> str:
@@ -88,7 +92,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False) -
         obj = OBJ / (src.parent.name + "_" + src.stem + ".o")
         objs.append(obj)
         if force or _needs(obj, src, hdr_mtime):
-            extra = torch_flags if src.suffix == ".cpp" else []
+            extra = torch_flags if src.suffix == ".cpp" else NO_PACKED_FP32.get(src.name, [])
             lang = ["-x", "hip"] if src.suffix == ".cpp" else []
             cmds.append([hipcc, *common, *extra, *lang, "-MMD", "-MF", str(obj.with_suffix(".d")), "-c",
                          str(src), "-o", str(obj)])

@@ -155,6 +155,13 @@ def load_snapshot(path: str, trainer) -> int:
     framework wrote are loaded, and with ``weights_only=True``."""
     d = torch.load(path, map_location="cpu", weights_only=True)
     st = trainer.state_tensors()
+    # a BatchNorm model's snapshot carries running statistics, a GroupNorm
+    # model's none: the other kind is refused before anything is written
+    have = {k for k in d["state"] if k.startswith("buf.")}
+    want = {k for k in st if k.startswith("buf.")}
+    if have != want:
+        raise ValueError(f"snapshot {path}: it holds {len(have)} model buffers, the trainer {len(want)} (a "
+                         "snapshot restores only into a trainer of the same model and norm)")
     for k, v in d["state"].items():
         # a snapshot of the other optimizer-state format (Trainer opt_dtype)
         # is refused before anything is written: neither a silent cast nor a

@@ -151,6 +151,7 @@ class ReplayJob:
     attn_dropout: Optional[float] = None     # attention-probability dropout of the job (None = off)
     opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" / "factored" (None = fp32)
     trust_ratio: Optional[float] = None  # layer-wise trust coefficient of the job: LARS / LAMB (None = off)
+    norm: Optional[str] = None           # normalisation of a CNN job: "batch" / "group" (None = batch)
 
 
 class Controller:
@@ -513,6 +514,7 @@ class Controller:
         for req in self.spool.poll():
             try:
                 jid, model, g, iters, batch, clip, drop, adrop, odt, eta = self._validate(req)
+                norm = self._validate_norm(req, model)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -525,7 +527,8 @@ class Controller:
             spec = JobSpec(job_id=jid, submit_time=now, duration=iters * self._iter_est(model, g),
                            num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
-                                        dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta)
+                                        dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta,
+                                        norm=norm)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -608,6 +611,18 @@ class Controller:
                 raise ValueError(f"trust_ratio is not supported with opt_dtype {odt!r}")
         return jid, model, g, iters, batch, clip, drop, adrop, odt, eta
 
+    @staticmethod
+    def _validate_norm(req: dict, model: str) -> Optional[str]:
+        """The request's ``norm`` key (absent / null: None, the model's own
+        normalisation); ValueError for a value that is not one or a model
+        without BatchNorm layers."""
+        from .trainer import check_norm
+
+        norm = req.get("norm")
+        if norm is not None:
+            check_norm(model, norm)
+        return norm
+
     def status(self) -> dict:
         s = self.sched
         jobs = {}
@@ -670,6 +685,8 @@ class Controller:
                        "batch": rj.batch, "grad_clip": rj.grad_clip, "dropout": rj.dropout,
                        "attn_dropout": rj.attn_dropout, "opt_dtype": rj.opt_dtype, "trust_ratio": rj.trust_ratio,
                        "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
+                if rj.norm is not None:        # (a job that did not ask: the action as it always was)
+                    act["norm"] = rj.norm
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
                     act["source"] = "snapshot"
@@ -910,9 +927,13 @@ class Worker:
         """Warm-pool key of a start action: what fixes a trainer's buffers.
         The optimizer-state format does (bf16 state buffers cannot serve a
         fp32-state job, nor the reverse), so a bf16- or factored-state job's key carries it;
-        the per-job setters (clip, dropouts, trust ratio) are not part of the key."""
+        the per-job setters (clip, dropouts, trust ratio) are not part of the key.
+        A GroupNorm job's model has other layers and no running statistics, so
+        its key carries ``norm`` too."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
-        return key + (act["opt_dtype"],) if act.get("opt_dtype") in ("bf16", "factored") else key
+        if act.get("opt_dtype") in ("bf16", "factored"):
+            key += (act["opt_dtype"],)
+        return key + ("norm=group",) if act.get("norm") == "group" else key
 
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
@@ -934,6 +955,9 @@ class Worker:
             if free[-1].opt_dtype != want_dt:
                 raise RuntimeError(f"warm pool {key}: a {free[-1].opt_dtype}-state trainer is pooled under the "
                                    f"key of a {want_dt}-state job")
+            if free[-1].norm != (act.get("norm") or "batch"):
+                raise RuntimeError(f"warm pool {key}: a norm={free[-1].norm} trainer is pooled under the key of a "
+                                   f"norm={act.get('norm') or 'batch'} job")
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
@@ -948,7 +972,7 @@ class Worker:
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
                     ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
                     attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"),
-                    trust_ratio=act.get("trust_ratio"))
+                    trust_ratio=act.get("trust_ratio"), norm=act.get("norm"))
         t.pool_key = key
         return t
 
@@ -1288,7 +1312,7 @@ class Worker:
                     t = self.trainers[a["job"]]
                     t.rebind(self._group(ranks))
                     # (the trainer's own state format, whatever the action carries)
-                    t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype))
+                    t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype, norm=t.norm))
                 elif self.rank in ranks:
                     self._bind(self.trainers[a["job"]], ranks)
                 if self.rank in ranks and "step" in a:

@@ -85,6 +85,7 @@ class FakeCluster:
         self.spilled: Set[str] = set()
         self.model: Dict[str, str] = {}
         self.odt: Dict[str, Optional[str]] = {}      # job -> optimizer-state format (start action's opt_dtype)
+        self.norm: Dict[str, Optional[str]] = {}     # job -> normalisation it was started with (start action's norm)
         self.groups: Set[Tuple[int, ...]] = set()
         self.stats = {"p2p_bytes": 0.0, "spill_bytes": 0.0, "restore_bytes": 0.0, "starts": 0,
                       "resident_resumes": 0, "rounds": 0}
@@ -174,6 +175,14 @@ class FakeCluster:
                     raise ProtocolError(f"gang {job} started on {ranks} without a communicator")
                 self.model[job] = a["model"]
                 self.odt[job] = a.get("opt_dtype")
+                # norm fixes a job's model: every start of a job carries the
+                # same one (GroupNorm adds no state and no cost to the world model)
+                if a.get("norm") not in (None, "batch", "group"):
+                    raise ProtocolError(f"start of {job} with norm {a.get('norm')!r}")
+                if job in self.held and self.norm.get(job) != a.get("norm"):
+                    raise ProtocolError(f"start of {job} with norm {a.get('norm')!r}, its state was built "
+                                        f"with {self.norm.get(job)!r}")
+                self.norm[job] = a.get("norm")
                 src = a["source"]
                 b = _state_bytes(a["model"], a.get("opt_dtype"))
                 if src == "fresh":

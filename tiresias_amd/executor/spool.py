@@ -20,6 +20,9 @@ Request schema (JSON)::
      "attn_dropout": null,          # attention-probability dropout, 0 <= p < 1 (quantised to 1/256)
      "opt_dtype": null,             # optimizer-state format, "fp32", "bf16" or "factored" (null = fp32)
      "trust_ratio": null}           # layer-wise trust coefficient > 0: LARS (sgd models) / LAMB (adam models)
+
+A job that asks for ``--norm`` carries one more key, ``"norm": "batch" |
+"group"`` (ResNet models); a request without it is written as before.
 """
 from __future__ import annotations
 
@@ -48,7 +51,8 @@ class Spool:
                duration: Optional[float] = None, job_id: Optional[str] = None,
                batch: Optional[int] = None, grad_clip: Optional[float] = None,
                dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
-               opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None) -> str:
+               opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
+               norm: Optional[str] = None) -> str:
         if iterations is None and duration is None:
             raise ValueError("give iterations or duration")
         jid = job_id or f"sub-{time.time_ns()}-{os.getpid()}"
@@ -56,6 +60,8 @@ class Spool:
                "duration": duration, "batch": batch, "grad_clip": grad_clip, "dropout": dropout,
                "attn_dropout": attn_dropout, "opt_dtype": opt_dtype,
                "trust_ratio": trust_ratio, "submitted_wall": time.time()}
+        if norm is not None:
+            req["norm"] = norm
         _atomic_write(os.path.join(self.root, "incoming", f"{jid}.json"), req)
         return jid
 

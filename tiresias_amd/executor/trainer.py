@@ -29,9 +29,15 @@ class Trainer:
                  overlap_wgrad: Optional[bool] = None, branches: Optional[bool] = None,
                  ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
                  dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
-                 opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None):
+                 opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
+                 norm: Optional[str] = None):
         self.model_name = model
         self.spec = MODELS[model]
+        # normalisation of a CNN job (README "GroupNorm"): "group" builds the
+        # model with GroupNorm in place of every BatchNorm. It changes the
+        # model's structure and buffers, so it is set at construction (and is
+        # part of the worker's warm-pool key), not by a per-job setter
+        self.norm = check_norm(model, self.spec.norm if norm is None else norm)
         if opt_dtype is None:
             opt_dtype = self.spec.opt_dtype
         if opt_dtype not in (None, "fp32", "bf16", "factored"):
@@ -76,7 +82,10 @@ class Trainer:
         self.batch = batch or self.spec.batch
         self.seed = seed
         self.arena = Arena(self.device, seed=seed)
-        self.model = make_model(model, self.arena, **(model_kwargs or {}))
+        mk = dict(model_kwargs or {})
+        if self.norm == "group":
+            mk["norm"] = "group"
+        self.model = make_model(model, self.arena, **mk)
         self.arena.materialize()
         n = self.arena.numel
         self.opt = self.spec.opt
@@ -936,6 +945,19 @@ class Trainer:
         self._g_loss = None
         self.last_loss = None                    # may alias the graph's output
         self.arena.on_grad_ready = None
+
+
+def check_norm(model: str, norm) -> str:
+    """The normalisation a job of ``model`` runs with ("batch" when ``norm`` is
+    None); ValueError for a value that is not one, or for a model that has no
+    BatchNorm layers to replace."""
+    if norm is None:
+        return "batch"
+    if not isinstance(norm, str) or norm not in ("batch", "group"):
+        raise ValueError(f"norm must be 'batch' or 'group', got {norm!r}")
+    if norm not in getattr(MODELS[model].builder, "norms", ()):
+        raise ValueError(f"norm={norm!r}: {model!r} has no BatchNorm layers (the knob is for the ResNet models)")
+    return norm
 
 
 def _check_trust_ratio(v) -> float:

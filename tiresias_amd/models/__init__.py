@@ -60,6 +60,10 @@ class ModelSpec:
     # --trust-ratio): LARS for an sgd model, LAMB for an adam model; None =
     # off. No shipped model sets it
     trust_ratio: Optional[float] = None
+    # normalisation of a CNN job (Trainer norm, --norm): None / "batch" keep
+    # BatchNorm, "group" builds the model with GroupNorm instead (ResNet
+    # models; others reject it). No shipped model sets it
+    norm: Optional[str] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

@@ -40,12 +40,20 @@ class ResNet50:
     """torchvision-style ResNet-50 v1.5 (stride on the 3x3 conv), NHWC."""
 
     name = "resnet50"
+    norms = ("batch", "group")     # what Trainer(norm=) / submit --norm may ask of this model
 
     def __init__(self, arena: Arena, num_classes: int = 1000, layers=(3, 4, 6, 3), width: int = 64,
-                 in_ch: int = 8):
+                 in_ch: int = 8, norm: str = "batch"):
+        if norm not in ("batch", "group"):
+            raise ValueError(f"norm must be 'batch' or 'group', got {norm!r}")
         self.arena = arena
         dev = arena.device
         self.training = True
+        # "group": every normalisation is a GroupNorm (Fx.groupnorm) over the
+        # same gamma / beta parameters, same names and arena order; no running
+        # statistics, no statistics workspaces, and the convs run without the
+        # BN-statistics epilogue and without the in_relu mask hand-off
+        self.norm = norm
         A = arena
         self.stem = A.add("stem.conv", (width, 7, 7, in_ch), init="kaiming")
         self.stem_bn = (A.add("stem.bn.g", (width,), init="ones", decay=False, fp32_compute=True),
@@ -77,14 +85,26 @@ class ResNet50:
                 blk["pre"] = pre
                 self.blocks.append(blk)
                 cin = w * 4
-        self.bn_buf, self.bn_ws = Fx.bn_workspaces(
-            {k: st.mean.numel() for k, st in self.bn_state.items()}, dev)
+        if norm == "group":
+            self.bn_state = {}
+            self.bn_buf, self.bn_ws = None, {}
+        else:
+            self.bn_buf, self.bn_ws = Fx.bn_workspaces(
+                {k: st.mean.numel() for k, st in self.bn_state.items()}, dev)
         self.fc_w = A.add("fc.w", (num_classes, cin), init="normal", std=0.01)
         self.fc_b = A.add("fc.b", (num_classes,), init="zeros", decay=False)
         self.num_classes = num_classes
         self.in_ch = in_ch
 
+    @staticmethod
+    def gn_groups(C: int) -> int:
+        """Groups of a C-channel GroupNorm: 32 from C = 64 upwards, never fewer
+        than 2 channels per group (resnet_tiny's 8-channel layers: 4 groups)."""
+        return C // max(2, C // 32)
+
     def _bn(self, x, p, key, relu, res=None, consumer_masks=False):
+        if self.norm == "group":
+            return Fx.groupnorm(x, p[0], p[1], self.gn_groups(x.shape[-1]), relu=relu, residual=res)
         st = self.bn_state[key]
         return Fx.batchnorm(x, p[0], p[1], st.mean, st.var, relu=relu, residual=res,
                             training=self.training, consumer_masks=consumer_masks,
@@ -93,6 +113,9 @@ class ResNet50:
     def _st(self, key):
         # the conv feeding BN `key` accumulates its statistics into the BN's
         # forward workspace (training on GPU), else the BN reduces itself
+        # (a GroupNorm takes its own statistics: no epilogue)
+        if self.norm == "group":
+            return False
         return self.bn_ws[key].fwd if (self.training and self.bn_buf.is_cuda) else True
 
     def conv_params(self):
@@ -103,7 +126,8 @@ class ResNet50:
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         Fx.prepare_conv_wt(self.conv_params())
-        if self.training:
+        gn = self.norm == "group"
+        if self.training and not gn:
             # every BN accumulator of this step: one zeroing launch of ours
             if self.bn_buf.is_cuda:
                 Fx._T().zero_(self.bn_buf)
@@ -123,10 +147,10 @@ class ResNet50:
             # epilogue applies their ReLU backward mask (in_relu)
             o = Fx.conv2d(y, blk["c1"], bn_stats=self._st(pre + ".bn1"))
             o = self._bn(o, blk["bn1"], pre + ".bn1", relu=True, consumer_masks=True)
-            o = Fx.conv2d(o, blk["c2"], stride=blk["stride"], pad=1, in_relu=True,
+            o = Fx.conv2d(o, blk["c2"], stride=blk["stride"], pad=1, in_relu=not gn,
                           bn_stats=self._st(pre + ".bn2"))
             o = self._bn(o, blk["bn2"], pre + ".bn2", relu=True, consumer_masks=True)
-            o = Fx.conv2d(o, blk["c3"], in_relu=True, bn_stats=self._st(pre + ".bn3"))
+            o = Fx.conv2d(o, blk["c3"], in_relu=not gn, bn_stats=self._st(pre + ".bn3"))
             if "down" in blk:
                 idn = Fx.conv2d(y2, blk["down"], stride=blk["stride"],
                                 bn_stats=self._st(pre + ".dbn"))

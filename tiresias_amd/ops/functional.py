@@ -761,6 +761,100 @@ def batchnorm(x: torch.Tensor, g: Param, b: Param, run_mean: Optional[torch.Tens
     return y
 
 
+# ============================================================ GroupNorm (NHWC)
+# Statistics per (sample, group): a job's numerics do not depend on its batch,
+# its gang width or packing. No running statistics, no workspace, no mask
+# hand-off: the backward applies its own ReLU mask from y. The residual tap
+# (GradSlot / addend) is BatchNorm's.
+_GN_TILE = 256              # csrc/include/tam/kernels.h GN_TILE
+
+
+class _GN(Function):
+    @staticmethod
+    def forward(ctx, x, res, token, g: Param, b: Param, groups: int, relu: bool, eps: float,
+                slot: Optional[GradSlot] = None):
+        N, C = x.shape[0], x.shape[-1]
+        if x.is_cuda:
+            y = torch.empty_like(x)
+            mean = torch.empty(N * groups, dtype=torch.float32, device=x.device)
+            rstd = torch.empty_like(mean)
+            _T().groupnorm_forward(x, res, y, g.master, b.master, mean, rstd, groups, eps, relu)
+        else:
+            xf = x.float().reshape(N, -1, groups, C // groups)
+            mean = xf.mean((1, 3), keepdim=True)
+            rstd = torch.rsqrt(xf.var((1, 3), unbiased=False, keepdim=True) + eps)
+            yf = ((xf - mean) * rstd).reshape(N, -1, C) * g.master + b.master
+            if res is not None:
+                yf = yf + res.float().reshape(N, -1, C)
+            if relu:
+                yf = yf.clamp_min(0)
+            y = yf.reshape(x.shape).to(BF16)
+        ctx.g, ctx.b, ctx.groups, ctx.relu, ctx.has_res, ctx.slot = g, b, groups, relu, res is not None, slot
+        ctx.save_for_backward(x, y if relu else None, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, mean, rstd = ctx.saved_tensors
+        g, b, G = ctx.g, ctx.b, ctx.groups
+        dy = dy.contiguous()
+        N, C = x.shape[0], x.shape[-1]
+        add = None
+        if ctx.slot is not None:
+            add, ctx.slot.stash = ctx.slot.stash, None
+        if dy.is_cuda:
+            dx = torch.empty_like(x)
+            dres = torch.empty_like(x) if ctx.has_res and (ctx.relu or add is not None) else None
+            tiles = (x.numel() // (N * C) + _GN_TILE - 1) // _GN_TILE
+            cpart = torch.empty(N * tiles * 2 * C, dtype=torch.float32, device=x.device)
+            deferred = _DEFER_WGRAD is not None and LN_DEFER
+            nblk = _T().groupnorm_backward(dy, y, x, mean, rstd, g.master, dx, dres, cpart,
+                                           None if deferred else g.grad, None if deferred else b.grad, G,
+                                           ctx.relu, add)
+            if ctx.has_res and dres is None:
+                dres = dy
+            if deferred:                   # dgamma | dbeta ride the backward's one batched column reduce
+                _DEFER_LNRED.append((cpart, nblk, g, b))
+                return dx, dres, None, None, None, None, None, None, None
+        else:
+            dyf = dy.float().reshape(N, -1, C)
+            if add is not None:
+                dyf = dyf + add.float().reshape(N, -1, C)
+            if ctx.relu:
+                dyf = dyf * (y.float().reshape(N, -1, C) > 0)
+            xh = (x.float().reshape(N, -1, G, C // G) - mean) * rstd
+            g.grad += (dyf * xh.reshape(N, -1, C)).sum((0, 1))
+            b.grad += dyf.sum((0, 1))
+            gd = (dyf * g.master).reshape(xh.shape)
+            dxf = rstd * (gd - gd.mean((1, 3), keepdim=True) - xh * (gd * xh).mean((1, 3), keepdim=True))
+            dx = dxf.reshape(x.shape).to(BF16)
+            dres = dyf.reshape(x.shape).to(BF16) if ctx.has_res else None
+        g.grad_ready()
+        b.grad_ready()
+        return dx, dres, None, None, None, None, None, None, None
+
+
+def groupnorm(x: torch.Tensor, g: Param, b: Param, groups: int, relu: bool = False,
+              residual: Optional[torch.Tensor] = None, eps: float = 1e-5) -> torch.Tensor:
+    """y = relu(GN(x) + residual): ``groups`` groups over the last (channel)
+    dim of an NHWC tensor, statistics per sample. C % 8 == 0, C <= 2048 and
+    C / groups a power of two in [2, 256]; anything else raises."""
+    C = x.shape[-1]
+    cg = C // groups if groups > 0 and C % groups == 0 else 0
+    if C % 8 or C > 2048 or cg < 2 or cg > 256 or cg & (cg - 1):
+        raise ValueError(f"groupnorm: C = {C}, groups = {groups}: needs C % 8 == 0, C <= 2048 and C / groups "
+                         "a power of two in [2, 256]")
+    if not x.is_contiguous():
+        x = x.contiguous()
+    if residual is not None and not residual.is_contiguous():
+        residual = residual.contiguous()
+    slot = GradSlot() if (x.is_cuda and torch.is_grad_enabled()) else None
+    y = _GN.apply(x, residual, g.arena.token, g, b, groups, relu, eps, slot)
+    if slot is not None:
+        y._tam_slot = slot
+    return y
+
+
 # ============================================================ dropout
 # Training dropout without stored masks: the mask of a dropout call is a pure
 # function of the trainer's dropout record (int32[4] {seed, stream, step, 0},
