@@ -678,6 +678,93 @@ void conv_weight_t_batch_op(at::TensorList w, at::TensorList wt) {
   }
 }
 
+// Grouped 3x3 conv (conv_grouped.hip). The shapes the kernels serve are checked
+// here, before any launch: nothing else falls back
+struct GconvShape { int N, H, W, C, Cg, P, Q; };
+static GconvShape gconv_shape(const Tensor& x, const Tensor& w, int64_t stride, const char* op) {
+  check_bf16(x, "x"); check_contig(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0, op, ": x must be [N,H,W,C]");
+  TORCH_CHECK(w.dim() == 4 && w.size(1) == 3 && w.size(2) == 3, op, ": the filter must be 3x3, w [C,3,3,Cg]");
+  TORCH_CHECK(stride == 1 || stride == 2, op, ": stride must be 1 or 2, got ", stride);
+  const int64_t C = x.size(3), Cg = w.size(3);
+  TORCH_CHECK(w.size(0) == C && C % 16 == 0, op, ": K == C and C % 16 == 0, got C = ", C, ", K = ", w.size(0));
+  TORCH_CHECK((Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32) && C % Cg == 0, op,
+              ": channels per group must be 4, 8, 16 or 32 and divide C, got ", Cg);
+  TORCH_CHECK(x.numel() < (int64_t(1) << 31), op, ": x must have fewer than 2^31 elements");
+  const int H = (int)x.size(1), W = (int)x.size(2);
+  return {(int)x.size(0), H, W, (int)C, (int)Cg, (H - 1) / (int)stride + 1, (W - 1) / (int)stride + 1};
+}
+static void gconv_img(const Tensor& img, const GconvShape& g, const Tensor& x, const char* op) {
+  check_bf16(img, "img"); check_contig(img, "img");
+  TORCH_CHECK(img.numel() == tam::gconv_image_elems(g.C, g.Cg) && img.device() == x.device(), op,
+              ": img must be the packed image of w (gconv_pack)");
+}
+static void gconv_out(const Tensor& y, const GconvShape& g, const Tensor& x, const char* name, const char* op) {
+  check_bf16(y, name); check_contig(y, name);
+  TORCH_CHECK(y.dim() == 4 && y.size(0) == g.N && y.size(1) == g.P && y.size(2) == g.Q && y.size(3) == g.C &&
+                  y.device() == x.device(), op, ": ", name, " must be [N,P,Q,C]");
+}
+
+int64_t gconv_image_elems_op(int64_t C, int64_t Cg) { return tam::gconv_image_elems((int)C, (int)Cg); }
+
+// every grouped weight of a model packed in one launch (per GP_MAX)
+void gconv_pack_op(at::TensorList w, at::TensorList img) {
+  TORCH_CHECK(w.size() == img.size(), "tam.gconv_pack: list sizes differ");
+  if (w.empty()) return;
+  hipStream_t st = cur_stream(w[0]);
+  for (size_t base = 0; base < w.size(); base += tam::GP_MAX) {
+    tam::GPBatch b{};
+    b.n = (int)std::min<size_t>(tam::GP_MAX, w.size() - base);
+    for (int i = 0; i < b.n; ++i) {
+      const Tensor& a = w[base + i];
+      const Tensor& t = img[base + i];
+      check_bf16(a, "w"); check_bf16(t, "img"); check_contig(a, "w"); check_contig(t, "img");
+      TORCH_CHECK(a.dim() == 4 && a.size(1) == 3 && a.size(2) == 3, "tam.gconv_pack: w must be [C,3,3,Cg]");
+      const int64_t C = a.size(0), Cg = a.size(3);
+      TORCH_CHECK(C % 16 == 0 && (Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32) && C % Cg == 0,
+                  "tam.gconv_pack: C % 16 == 0 and Cg in {4, 8, 16, 32}, got C = ", C, ", Cg = ", Cg);
+      TORCH_CHECK(t.numel() == tam::gconv_image_elems((int)C, (int)Cg) && t.device() == a.device(),
+                  "tam.gconv_pack: img must hold gconv_image_elems(C, Cg) elements");
+      b.e[i].w = bp(a); b.e[i].img = bpm(t); b.e[i].C = (int)C; b.e[i].Cg = (int)Cg;
+    }
+    tam::gconv_pack_batch(b, st);
+  }
+}
+
+void gconv_fwd_op(const Tensor& x, const Tensor& w, const Tensor& img, const Tensor& y, int64_t stride) {
+  const char* op = "tam.gconv_fwd";
+  const GconvShape g = gconv_shape(x, w, stride, op);
+  gconv_img(img, g, x, op); gconv_out(y, g, x, "y", op);
+  tam::gconv_fwd(bp(x), bp(img), bpm(y), g.N, g.H, g.W, g.C, g.Cg, (int)stride, cur_stream(x));
+}
+
+// dx is x-shaped; mask (optional, x-shaped): dx stored only where mask > 0
+void gconv_dgrad_op(const Tensor& dy, const Tensor& w, const Tensor& img, const Tensor& dx, int64_t stride,
+                    const optional<Tensor>& mask) {
+  const char* op = "tam.gconv_dgrad";
+  const GconvShape g = gconv_shape(dx, w, stride, op);
+  gconv_img(img, g, dx, op); gconv_out(dy, g, dx, "dy", op);
+  if (mask.has_value() && mask->defined()) {
+    check_bf16(*mask, "mask"); check_contig(*mask, "mask");
+    TORCH_CHECK(mask->sizes() == dx.sizes() && mask->device() == dx.device(), op, ": mask must match dx");
+  }
+  tam::gconv_dgrad(bp(dy), bp(img), bpm(dx), opt_ptr<const tam::bf16_t>(mask), g.N, g.H, g.W, g.C, g.Cg, (int)stride,
+                   cur_stream(dx));
+}
+
+// dw [C,3,3,Cg] fp32 += the weight gradient (accumulates, like conv_wgrad into
+// the optimizer-zeroed buffer)
+void gconv_wgrad_op(const Tensor& dy, const Tensor& x, const Tensor& dw, int64_t stride) {
+  const char* op = "tam.gconv_wgrad";
+  const GconvShape g = gconv_shape(x, dw, stride, op);
+  gconv_out(dy, g, x, "dy", op);
+  check_f32(dw, "dw"); check_contig(dw, "dw");
+  TORCH_CHECK(dw.device() == x.device(), op, ": dw must be on x's device");
+  Tensor ws = at::empty({tam::gconv_wgrad_ws(g.N, g.H, g.W, g.C, g.Cg, (int)stride)}, x.options().dtype(at::kFloat));
+  tam::gconv_wgrad(bp(dy), bp(x), dw.data_ptr<float>(), ws.data_ptr<float>(), g.N, g.H, g.W, g.C, g.Cg, (int)stride,
+                   cur_stream(x));
+}
+
 // dgrad with wt already re-laid (conv_weight_t_batch)
 // stats / bnx / bnmean / bnrstd (all or none): dx is the gradient of a
 // BatchNorm output whose input was bnx; the dgrad epilogue then accumulates
@@ -1734,6 +1821,11 @@ TORCH_LIBRARY(tam, m) {
   m.def("gemm_wgrad_grouped(Tensor[] dy, Tensor[] x, Tensor(a!)[] dw, Tensor(b!)[] db, int[]? modes=None) -> ()", &gemm_wgrad_grouped_op);
   m.def("gemm_wgrad_grouped_ok(int M, int N, int K) -> bool", &gemm_wgrad_grouped_ok_op);
   m.def("gemm_grouped_tile(int tile) -> ()", &gemm_grouped_tile_op);
+  m.def("gconv_image_elems(int C, int Cg) -> int", &gconv_image_elems_op);
+  m.def("gconv_pack(Tensor[] w, Tensor(a!)[] img) -> ()", &gconv_pack_op);
+  m.def("gconv_fwd(Tensor x, Tensor w, Tensor img, Tensor(a!) y, int stride) -> ()", &gconv_fwd_op);
+  m.def("gconv_dgrad(Tensor dy, Tensor w, Tensor img, Tensor(a!) dx, int stride, Tensor? mask=None) -> ()", &gconv_dgrad_op);
+  m.def("gconv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int stride) -> ()", &gconv_wgrad_op);
   m.def("conv_dgrad_pre(Tensor dy, Tensor w, Tensor wt, Tensor(a!) dx, int stride, int pad, int dil, Tensor? mask, Tensor(b!)? stats=None, Tensor? bnx=None, Tensor? bnmean=None, Tensor? bnrstd=None) -> int", &conv_dgrad_pre_op);
   m.def("conv_wgrad(Tensor dy, Tensor x, Tensor(a!) dw, int stride, int pad, int dil, int mode, Tensor(b!)? dbias=None, bool patch=True) -> ()", &conv_wgrad_op);
   m.def("conv_wgrad_deferred(Tensor dy, Tensor x, Tensor(a!) dw, int stride, int pad, int dil, int mode, Tensor(b!)? dbias, bool patch) -> (Tensor, int)", &conv_wgrad_deferred_op);

@@ -123,6 +123,33 @@ void conv_wgrad_force(int bm, int bn, int splits, int noatomic = 0);
 void conv_wgrad_order(int flat);    // DMA wgrad block order: 1 split-major XCD remap (default), 0 3-D grid
 void conv_wgrad_c64_policy(int p);   // 64-channel 3x3 wgrad kernel: 1 on (default), 0 off, >= 2 blocks per k-slice
 void conv_halo_policy(int p);   // 1: 64-channel 3x3 stride-1 passes on the halo-tile kernel (default)
+// Grouped 3x3 conv (conv_grouped.hip): bf16 NHWC x / y [N][H][W][C], pad 1,
+// stride 1 or 2, K == C, w [C][3][3][Cg], Cg in {4, 8, 16, 32}, C % 16 == 0
+// (checked by the caller). The kernels read packed block-diagonal images, not w:
+// gconv_image_elems(C, Cg) bf16 per weight (forward image | data-gradient image),
+// written for up to GP_MAX weights by one gconv_pack_batch launch.
+struct GPEntry {
+  const bf16_t* w;
+  bf16_t* img;
+  int C, Cg, blk0;
+};
+constexpr int GP_MAX = 64;
+struct GPBatch {
+  int n;
+  GPEntry e[GP_MAX];
+};
+long gconv_image_elems(int C, int Cg);
+void gconv_pack_batch(GPBatch& b, hipStream_t s);
+void gconv_fwd(const bf16_t* x, const bf16_t* img, bf16_t* y, int N, int H, int W, int C, int Cg, int stride,
+               hipStream_t s);
+// dx [N][H][W][C] from dy [N][P][Q][C]; mask (optional, dx's shape): dx = 0 where mask <= 0
+void gconv_dgrad(const bf16_t* dy, const bf16_t* img, bf16_t* dx, const bf16_t* mask, int N, int H, int W, int C,
+                 int Cg, int stride, hipStream_t s);
+// dw [C][3][3][Cg] fp32 += the weight gradient; ws: gconv_wgrad_ws(...) floats of
+// per-block partials (a function of the shape, not of the data); no atomics
+long gconv_wgrad_ws(int N, int H, int W, int C, int Cg, int stride);
+void gconv_wgrad(const bf16_t* dy, const bf16_t* x, float* dw, float* ws, int N, int H, int W, int C, int Cg,
+                 int stride, hipStream_t s);
 bool gemm_select_big_p8(bool ak, bool bk, int M, int N, int K, long lda, long ldb);   // plain-GEMM igemm K-tiles in flight (1..3)
 
 }  // namespace tam

@@ -165,11 +165,13 @@ def load_snapshot(path: str, trainer) -> int:
     for k, v in d["state"].items():
         # a snapshot of the other optimizer-state format (Trainer opt_dtype)
         # is refused before anything is written: neither a silent cast nor a
-        # reinterpretation of its bytes
+        # reinterpretation of its bytes. A snapshot of another cardinality
+        # (Trainer cardinality: other bottleneck widths) has another arena size
+        # and is refused here too
         if k in st and (v.dtype != st[k].dtype or v.numel() != st[k].numel()):
             raise ValueError(f"snapshot {path}: buffer {k!r} is {v.dtype} x {v.numel()}, the trainer holds "
                              f"{st[k].dtype} x {st[k].numel()} (a snapshot restores only into a trainer of "
-                             "the same model and opt_dtype)")
+                             "the same model, cardinality and opt_dtype)")
     for k, v in d["state"].items():
         if k in st:
             st[k].copy_(v, non_blocking=False)

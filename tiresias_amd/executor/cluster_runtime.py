@@ -152,6 +152,7 @@ class ReplayJob:
     opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" / "factored" (None = fp32)
     trust_ratio: Optional[float] = None  # layer-wise trust coefficient of the job: LARS / LAMB (None = off)
     norm: Optional[str] = None           # normalisation of a CNN job: "batch" / "group" (None = batch)
+    cardinality: Optional[int] = None    # ResNeXt cardinality of a ResNet job (None = the plain model)
 
 
 class Controller:
@@ -515,6 +516,7 @@ class Controller:
             try:
                 jid, model, g, iters, batch, clip, drop, adrop, odt, eta = self._validate(req)
                 norm = self._validate_norm(req, model)
+                card = self._validate_cardinality(req, model)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -528,7 +530,7 @@ class Controller:
                            num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
                                         dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta,
-                                        norm=norm)
+                                        norm=norm, cardinality=card)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -623,6 +625,15 @@ class Controller:
             check_norm(model, norm)
         return norm
 
+    @staticmethod
+    def _validate_cardinality(req: dict, model: str) -> Optional[int]:
+        """The request's ``cardinality`` key (absent / null: None, the plain
+        model); ValueError for a value that is not one or a model without a
+        bottleneck to group."""
+        from .trainer import check_cardinality
+
+        return check_cardinality(model, req.get("cardinality"))
+
     def status(self) -> dict:
         s = self.sched
         jobs = {}
@@ -687,6 +698,8 @@ class Controller:
                        "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
                 if rj.norm is not None:        # (a job that did not ask: the action as it always was)
                     act["norm"] = rj.norm
+                if rj.cardinality is not None:
+                    act["cardinality"] = rj.cardinality
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
                     act["source"] = "snapshot"
@@ -929,11 +942,13 @@ class Worker:
         fp32-state job, nor the reverse), so a bf16- or factored-state job's key carries it;
         the per-job setters (clip, dropouts, trust ratio) are not part of the key.
         A GroupNorm job's model has other layers and no running statistics, so
-        its key carries ``norm`` too."""
+        its key carries ``norm`` too, and a ResNeXt job's its ``cardinality``."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
         if act.get("opt_dtype") in ("bf16", "factored"):
             key += (act["opt_dtype"],)
-        return key + ("norm=group",) if act.get("norm") == "group" else key
+        if act.get("norm") == "group":
+            key += ("norm=group",)
+        return key + (f"cardinality={act['cardinality']}",) if act.get("cardinality") is not None else key
 
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
@@ -958,6 +973,9 @@ class Worker:
             if free[-1].norm != (act.get("norm") or "batch"):
                 raise RuntimeError(f"warm pool {key}: a norm={free[-1].norm} trainer is pooled under the key of a "
                                    f"norm={act.get('norm') or 'batch'} job")
+            if free[-1].cardinality != act.get("cardinality"):
+                raise RuntimeError(f"warm pool {key}: a cardinality={free[-1].cardinality} trainer is pooled under "
+                                   f"the key of a cardinality={act.get('cardinality')} job")
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
@@ -972,7 +990,8 @@ class Worker:
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
                     ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
                     attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"),
-                    trust_ratio=act.get("trust_ratio"), norm=act.get("norm"))
+                    trust_ratio=act.get("trust_ratio"), norm=act.get("norm"),
+                    cardinality=act.get("cardinality"))
         t.pool_key = key
         return t
 
@@ -1312,7 +1331,8 @@ class Worker:
                     t = self.trainers[a["job"]]
                     t.rebind(self._group(ranks))
                     # (the trainer's own state format, whatever the action carries)
-                    t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype, norm=t.norm))
+                    t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype, norm=t.norm,
+                                                        cardinality=t.cardinality))
                 elif self.rank in ranks:
                     self._bind(self.trainers[a["job"]], ranks)
                 if self.rank in ranks and "step" in a:

@@ -86,6 +86,7 @@ class FakeCluster:
         self.model: Dict[str, str] = {}
         self.odt: Dict[str, Optional[str]] = {}      # job -> optimizer-state format (start action's opt_dtype)
         self.norm: Dict[str, Optional[str]] = {}     # job -> normalisation it was started with (start action's norm)
+        self.card: Dict[str, Optional[int]] = {}     # job -> ResNeXt cardinality it was started with
         self.groups: Set[Tuple[int, ...]] = set()
         self.stats = {"p2p_bytes": 0.0, "spill_bytes": 0.0, "restore_bytes": 0.0, "starts": 0,
                       "resident_resumes": 0, "rounds": 0}
@@ -183,6 +184,15 @@ class FakeCluster:
                     raise ProtocolError(f"start of {job} with norm {a.get('norm')!r}, its state was built "
                                         f"with {self.norm.get(job)!r}")
                 self.norm[job] = a.get("norm")
+                # cardinality fixes a job's model the same way
+                card = a.get("cardinality")
+                if card is not None and (isinstance(card, bool) or not isinstance(card, int) or card % 4
+                                         or not 4 <= card <= 64):
+                    raise ProtocolError(f"start of {job} with cardinality {card!r}")
+                if job in self.held and self.card.get(job) != card:
+                    raise ProtocolError(f"start of {job} with cardinality {card!r}, its state was built with "
+                                        f"{self.card.get(job)!r}")
+                self.card[job] = card
                 src = a["source"]
                 b = _state_bytes(a["model"], a.get("opt_dtype"))
                 if src == "fresh":

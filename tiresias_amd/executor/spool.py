@@ -22,7 +22,8 @@ Request schema (JSON)::
      "trust_ratio": null}           # layer-wise trust coefficient > 0: LARS (sgd models) / LAMB (adam models)
 
 A job that asks for ``--norm`` carries one more key, ``"norm": "batch" |
-"group"`` (ResNet models); a request without it is written as before.
+"group"`` (ResNet models); a request without it is written as before. The
+same holds for ``--cardinality``: ``"cardinality": G`` (ResNeXt, ResNet models).
 """
 from __future__ import annotations
 
@@ -52,7 +53,7 @@ class Spool:
                batch: Optional[int] = None, grad_clip: Optional[float] = None,
                dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
                opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
-               norm: Optional[str] = None) -> str:
+               norm: Optional[str] = None, cardinality: Optional[int] = None) -> str:
         if iterations is None and duration is None:
             raise ValueError("give iterations or duration")
         jid = job_id or f"sub-{time.time_ns()}-{os.getpid()}"
@@ -62,6 +63,8 @@ class Spool:
                "trust_ratio": trust_ratio, "submitted_wall": time.time()}
         if norm is not None:
             req["norm"] = norm
+        if cardinality is not None:
+            req["cardinality"] = cardinality
         _atomic_write(os.path.join(self.root, "incoming", f"{jid}.json"), req)
         return jid
 

@@ -30,7 +30,7 @@ class Trainer:
                  ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
                  dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
                  opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
-                 norm: Optional[str] = None):
+                 norm: Optional[str] = None, cardinality: Optional[int] = None):
         self.model_name = model
         self.spec = MODELS[model]
         # normalisation of a CNN job (README "GroupNorm"): "group" builds the
@@ -38,6 +38,11 @@ class Trainer:
         # model's structure and buffers, so it is set at construction (and is
         # part of the worker's warm-pool key), not by a per-job setter
         self.norm = check_norm(model, self.spec.norm if norm is None else norm)
+        # ResNeXt cardinality of a ResNet job (README "ResNeXt"): G builds every
+        # bottleneck with a G-group 3x3 conv on the grouped conv kernels. Like
+        # norm it fixes the model's structure: set at construction, part of
+        # the worker's warm-pool key, no per-job setter
+        self.cardinality = check_cardinality(model, self.spec.cardinality if cardinality is None else cardinality)
         if opt_dtype is None:
             opt_dtype = self.spec.opt_dtype
         if opt_dtype not in (None, "fp32", "bf16", "factored"):
@@ -85,6 +90,8 @@ class Trainer:
         mk = dict(model_kwargs or {})
         if self.norm == "group":
             mk["norm"] = "group"
+        if self.cardinality is not None:
+            mk["cardinality"] = self.cardinality
         self.model = make_model(model, self.arena, **mk)
         self.arena.materialize()
         n = self.arena.numel
@@ -958,6 +965,21 @@ def check_norm(model: str, norm) -> str:
     if norm not in getattr(MODELS[model].builder, "norms", ()):
         raise ValueError(f"norm={norm!r}: {model!r} has no BatchNorm layers (the knob is for the ResNet models)")
     return norm
+
+
+def check_cardinality(model: str, v) -> Optional[int]:
+    """The ResNeXt cardinality a job of ``model`` runs with (None: the plain
+    model); ValueError for a value that is not an integer multiple of 4 in
+    [4, 64], or for a model whose builder has no bottleneck to group."""
+    if v is None:
+        return None
+    from ..models.cnn import check_cardinality_value
+
+    check_cardinality_value(v)
+    if not getattr(MODELS[model].builder, "cardinalities", False):
+        raise ValueError(f"cardinality={v!r}: {model!r} has no bottleneck 3x3 conv to group (the knob is for the "
+                         "ResNet models)")
+    return v
 
 
 def _check_trust_ratio(v) -> float:

@@ -64,6 +64,10 @@ class ModelSpec:
     # BatchNorm, "group" builds the model with GroupNorm instead (ResNet
     # models; others reject it). No shipped model sets it
     norm: Optional[str] = None
+    # ResNeXt cardinality of a ResNet job (Trainer cardinality, --cardinality):
+    # None keeps the plain bottleneck, G builds it with a G-group 3x3 conv
+    # (ResNet models; others reject it). No shipped model sets it
+    cardinality: Optional[int] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

@@ -36,16 +36,31 @@ class _BNState:
         self.var = torch.ones(C, dtype=torch.float32, device=device)
 
 
+def check_cardinality_value(v) -> None:
+    """ValueError unless ``v`` is None or a ResNeXt cardinality the grouped conv
+    kernels serve: an integer, a multiple of 4 in [4, 64]."""
+    if v is None:
+        return
+    if isinstance(v, bool) or not isinstance(v, int) or v % 4 or not 4 <= v <= 64:
+        raise ValueError(f"cardinality must be an integer multiple of 4 in [4, 64], got {v!r}")
+
+
 class ResNet50:
     """torchvision-style ResNet-50 v1.5 (stride on the 3x3 conv), NHWC."""
 
     name = "resnet50"
     norms = ("batch", "group")     # what Trainer(norm=) / submit --norm may ask of this model
+    cardinalities = True           # Trainer(cardinality=) / submit --cardinality: the ResNeXt variant
 
     def __init__(self, arena: Arena, num_classes: int = 1000, layers=(3, 4, 6, 3), width: int = 64,
-                 in_ch: int = 8, norm: str = "batch"):
+                 in_ch: int = 8, norm: str = "batch", cardinality=None, group_width: int = 4):
         if norm not in ("batch", "group"):
             raise ValueError(f"norm must be 'batch' or 'group', got {norm!r}")
+        check_cardinality_value(cardinality)
+        # cardinality G (ResNeXt, Xie et al. 2017): stage i's bottleneck width is
+        # G * group_width * 2^i, its 3x3 conv has G groups (Fx.conv2d groups=);
+        # None: the plain ResNet, same parameters and arena order as ever
+        self.cardinality = cardinality
         self.arena = arena
         dev = arena.device
         self.training = True
@@ -62,16 +77,17 @@ class ResNet50:
         self.blocks: List[dict] = []
         cin = width
         for si, (n, w) in enumerate(zip(layers, [width, width * 2, width * 4, width * 8])):
+            bw = w if cardinality is None else cardinality * group_width * 2 ** si    # bottleneck width
             for bi in range(n):
                 stride = 2 if (bi == 0 and si > 0) else 1
                 pre = f"s{si}.b{bi}"
                 blk = {
                     "stride": stride,
-                    "c1": A.add(pre + ".c1", (w, 1, 1, cin), init="kaiming"),
-                    "c2": A.add(pre + ".c2", (w, 3, 3, w), init="kaiming"),
-                    "c3": A.add(pre + ".c3", (w * 4, 1, 1, w), init="kaiming"),
+                    "c1": A.add(pre + ".c1", (bw, 1, 1, cin), init="kaiming"),
+                    "c2": A.add(pre + ".c2", (bw, 3, 3, bw // (cardinality or 1)), init="kaiming"),
+                    "c3": A.add(pre + ".c3", (w * 4, 1, 1, bw), init="kaiming"),
                 }
-                for k, c in (("bn1", w), ("bn2", w), ("bn3", w * 4)):
+                for k, c in (("bn1", bw), ("bn2", bw), ("bn3", w * 4)):
                     # zero-init the last BN gamma of each block (standard trick)
                     blk[k] = (A.add(f"{pre}.{k}.g", (c,), init="zeros" if k == "bn3" else "ones",
                                     decay=False, fp32_compute=True),
@@ -119,13 +135,25 @@ class ResNet50:
         return self.bn_ws[key].fwd if (self.training and self.bn_buf.is_cuda) else True
 
     def conv_params(self):
+        # the dense convs (re-laid for dgrad); grouped c2 weights have their own pack
         out = [self.stem]
         for blk in self.blocks:
-            out += [blk["c1"], blk["c2"], blk["c3"]] + ([blk["down"]] if "down" in blk else [])
+            out += [blk["c1"]] + ([blk["c2"]] if self.cardinality is None else []) + [blk["c3"]]
+            out += [blk["down"]] if "down" in blk else []
         return out
+
+    def _c2(self, o, blk, pre, gn):
+        if self.cardinality is None:
+            return Fx.conv2d(o, blk["c2"], stride=blk["stride"], pad=1, in_relu=not gn,
+                             bn_stats=self._st(pre + ".bn2"))
+        # no statistics epilogue on the grouped conv: bn2 reduces itself
+        return Fx.conv2d(o, blk["c2"], stride=blk["stride"], pad=1, in_relu=not gn,
+                         bn_stats=self._st(pre + ".bn2") is not False, groups=self.cardinality)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         Fx.prepare_conv_wt(self.conv_params())
+        if self.cardinality is not None:
+            Fx.prepare_gconv_w([blk["c2"] for blk in self.blocks])
         gn = self.norm == "group"
         if self.training and not gn:
             # every BN accumulator of this step: one zeroing launch of ours
@@ -147,8 +175,7 @@ class ResNet50:
             # epilogue applies their ReLU backward mask (in_relu)
             o = Fx.conv2d(y, blk["c1"], bn_stats=self._st(pre + ".bn1"))
             o = self._bn(o, blk["bn1"], pre + ".bn1", relu=True, consumer_masks=True)
-            o = Fx.conv2d(o, blk["c2"], stride=blk["stride"], pad=1, in_relu=not gn,
-                          bn_stats=self._st(pre + ".bn2"))
+            o = self._c2(o, blk, pre, gn)
             o = self._bn(o, blk["bn2"], pre + ".bn2", relu=True, consumer_masks=True)
             o = Fx.conv2d(o, blk["c3"], in_relu=not gn, bn_stats=self._st(pre + ".bn3"))
             if "down" in blk:

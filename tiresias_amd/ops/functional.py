@@ -544,15 +544,104 @@ def weight_kmajor(p: Param) -> Optional[torch.Tensor]:
     return wk if wk is not None and getattr(p, "wk_epoch", None) == p.arena.grad_epoch else None
 
 
+# ------------------------------------------------------------ grouped 3x3 conv
+# ResNeXt's bottleneck conv (csrc/kernels/conv_grouped.hip): weights
+# [C,3,3,Cg], K == C, pad 1, stride 1 or 2, Cg in {4, 8, 16, 32}, C % 16 == 0.
+# The kernels read packed block-diagonal images of the weight (p.gimg), made
+# for every grouped weight of a model by one launch per step.
+def _gconv_check(C: int, w: Param, stride: int, pad: int) -> int:
+    K, R, S, Cg = w.shape
+    if (R, S) != (3, 3) or pad != 1 or stride not in (1, 2):
+        raise ValueError(f"grouped conv2d: 3x3 / pad 1 / stride 1 or 2 only, got {R}x{S}, pad {pad}, stride {stride}")
+    if K != C or C % 16 or Cg not in (4, 8, 16, 32) or C % Cg:
+        raise ValueError(f"grouped conv2d: needs K == C, C % 16 == 0 and C / groups in (4, 8, 16, 32); got "
+                         f"C = {C}, K = {K}, C / groups = {Cg}")
+    return C // Cg
+
+
+def prepare_gconv_w(params: List[Param]) -> None:
+    """Pack every grouped conv weight [C,3,3,Cg] into the images its kernels
+    read (forward | data gradient) in ONE launch per step, into per-parameter
+    buffers kept across steps. Call at the start of the forward, like
+    ``prepare_conv_wt``. No-op on CPU."""
+    if not params or not params[0].w.is_cuda:
+        return
+    for p in params:
+        if getattr(p, "gimg", None) is None or p.gimg.device != p.w.device:
+            p.gimg = torch.empty(_T().gconv_image_elems(p.shape[0], p.shape[3]), dtype=BF16, device=p.w.device)
+        p.gimg_epoch = p.arena.grad_epoch
+    _T().gconv_pack([p.w for p in params], [p.gimg for p in params])
+
+
+def _gconv_img(w: Param) -> torch.Tensor:
+    """w's packed images: this step's from prepare_gconv_w, else packed here."""
+    if getattr(w, "gimg", None) is None or getattr(w, "gimg_epoch", None) != w.arena.grad_epoch:
+        prepare_gconv_w([w])
+    return w.gimg
+
+
+class _GConv(Function):
+    @staticmethod
+    def forward(ctx, x, token, w: Param, stride: int, in_relu: bool):
+        N, H, W, C = x.shape
+        if x.is_cuda:
+            y = torch.empty(N, _conv_out(H, 3, stride, 1), _conv_out(W, 3, stride, 1), C, dtype=BF16, device=x.device)
+            _T().gconv_fwd(x, w.w, _gconv_img(w), y, stride)
+        else:
+            yf = F.conv2d(x.float().permute(0, 3, 1, 2), w.w.float().permute(0, 3, 1, 2), stride=stride,
+                          padding=1, groups=C // w.shape[3])
+            y = yf.permute(0, 2, 3, 1).contiguous().to(BF16)
+        ctx.w, ctx.stride, ctx.in_relu = w, stride, in_relu
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        w, st = ctx.w, ctx.stride
+        dy = dy.contiguous()
+        dx = None
+        if dy.is_cuda:
+            # never deferred into the grouped GEMM launch: the reduction is the kernel's own
+            _T().gconv_wgrad(dy, x, w.grad, st)
+            if ctx.needs_input_grad[0]:
+                dx = torch.empty_like(x)
+                _T().gconv_dgrad(dy, w.w, _gconv_img(w), dx, st, x if ctx.in_relu else None)
+        else:
+            xf = x.float().permute(0, 3, 1, 2).requires_grad_(ctx.needs_input_grad[0])
+            wf = w.w.float().permute(0, 3, 1, 2).requires_grad_(True)
+            with torch.enable_grad():
+                yf = F.conv2d(xf, wf, stride=st, padding=1, groups=x.shape[-1] // w.shape[3])
+                grads = torch.autograd.grad(yf, [xf, wf] if ctx.needs_input_grad[0] else [wf],
+                                            dy.float().permute(0, 3, 1, 2))
+            if ctx.needs_input_grad[0]:
+                dxf = grads[0].permute(0, 2, 3, 1)
+                if ctx.in_relu:
+                    dxf = dxf * (x.float() > 0)
+                dx = dxf.contiguous().to(BF16)
+            w.grad += grads[-1].permute(0, 2, 3, 1)
+        w.grad_ready()
+        return dx, None, None, None, None
+
+
 def conv2d(x: torch.Tensor, w: Param, b: Optional[Param] = None, stride: int = 1, pad: int = 0,
            relu: bool = False, in_relu: bool = False, mask_own_relu: bool = True,
-           bn_stats=False) -> torch.Tensor:
+           bn_stats=False, groups: int = 1) -> torch.Tensor:
     """NHWC conv, weights [K,R,S,C]. ``bn_stats``: the output feeds a
     BatchNorm -- its per-channel sums come from the conv epilogue (where the
     conv path supports it) and ride on the output tensor. True, or the BN's
-    zeroed fp64 forward workspace (``BNWorkspace.fwd``) to accumulate into."""
+    zeroed fp64 forward workspace (``BNWorkspace.fwd``) to accumulate into.
+    ``groups`` > 1: the grouped 3x3 conv (weights [C,3,3,C/groups], pad 1,
+    stride 1 or 2); no bias, ReLU or statistics epilogue -- ``bn_stats=True``
+    is taken as a route without the epilogue (the BatchNorm reduces itself)."""
     if not x.is_contiguous():
         x = x.contiguous()
+    if groups != 1:
+        if b is not None or relu or isinstance(bn_stats, torch.Tensor):
+            raise ValueError("grouped conv2d: no bias, ReLU or BatchNorm-statistics epilogue")
+        if _gconv_check(x.shape[-1], w, stride, pad) != groups:
+            raise ValueError(f"grouped conv2d: groups = {groups} does not match w {tuple(w.shape)}")
+        return _GConv.apply(x, w.arena.token, w, stride, in_relu)
     y = _Conv.apply(x, w.arena.token, w, b, stride, pad, relu, in_relu, mask_own_relu, bn_stats)
     if bn_stats is not False and bn_stats is not None and y.is_cuda and y.grad_fn is not None:
         part = getattr(y.grad_fn, "part", None)
