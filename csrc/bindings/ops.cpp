@@ -1041,6 +1041,119 @@ bool gn_resident_fits_op(int64_t P, int64_t C, int64_t groups, bool backward) {
   return tam::gn_resident_fits((int)P, (int)C, (int)groups, backward ? 1 : 0);
 }
 
+// Squeeze-and-Excitation (se.hip): u [N, ..., C] (NHWC). The shapes the kernels
+// serve are checked here, before any launch: nothing else falls back
+struct SeShape { int N, P, C; };
+static SeShape se_shape(const Tensor& u, const char* op) {
+  check_bf16(u, "u"); check_contig(u, "u");
+  TORCH_CHECK(u.dim() >= 2 && u.numel() > 0, op, ": the activation must be [N, ..., C]");
+  const int64_t C = u.size(-1), N = u.size(0);
+  TORCH_CHECK(C % 8 == 0 && C <= 2048, op, ": C must be a multiple of 8 and <= 2048, got ", C);
+  const int64_t P = u.numel() / (N * C);
+  TORCH_CHECK(N <= 65535 && P * C < (int64_t(1) << 31), op, ": N <= 65535 and H*W*C < 2^31");
+  return {(int)N, (int)P, (int)C};
+}
+static void se_like(const Tensor& t, const Tensor& u, const char* name, const char* op) {
+  check_bf16(t, name); check_contig(t, name);
+  TORCH_CHECK(t.numel() == u.numel() && t.device() == u.device(), op, ": ", name, " must match the activation");
+}
+static void se_mat(const Tensor& t, int64_t rows, int64_t cols, const Tensor& like, const char* name, const char* op) {
+  check_f32(t, name);
+  TORCH_CHECK(t.is_contiguous() && t.numel() == rows * cols && t.device() == like.device() &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              op, ": ", name, " must be fp32 [", rows, ", ", cols, "], 16-byte aligned");
+}
+// z [N, C] and the two FC weights -> (N, C, Cr)
+static std::array<int, 3> se_fc_shape(const Tensor& z, const Tensor& w1, const Tensor& w2, const char* op) {
+  TORCH_CHECK(z.dim() == 2 && z.numel() > 0, op, ": z must be [N, C]");
+  const int64_t N = z.size(0), C = z.size(1);
+  se_mat(z, N, C, z, "z", op);
+  TORCH_CHECK(C % 8 == 0 && C <= 2048, op, ": C must be a multiple of 8 and <= 2048, got ", C);
+  TORCH_CHECK(w1.dim() == 2 && w1.size(1) == C, op, ": w1 must be [Cr, C]");
+  const int64_t Cr = w1.size(0);
+  TORCH_CHECK(Cr % 8 == 0 && Cr >= 8 && Cr <= 512, op, ": Cr must be a multiple of 8 in [8, 512], got ", Cr);
+  TORCH_CHECK(w2.dim() == 2 && w2.size(0) == C && w2.size(1) == Cr, op, ": w2 must be [C, Cr]");
+  TORCH_CHECK(N <= 65535, op, ": N <= 65535");
+  for (const Tensor* w : {&w1, &w2}) {
+    check_bf16(*w, "w"); check_contig(*w, "w");
+    TORCH_CHECK(w->device() == z.device() && reinterpret_cast<uintptr_t>(w->data_ptr()) % 16 == 0, op,
+                ": the weights must be on z's device, 16-byte aligned");
+  }
+  return {(int)N, (int)C, (int)Cr};
+}
+static void se_bias(const Tensor& b, int64_t n, const Tensor& like, const char* name, const char* op) {
+  check_bf16(b, name);
+  TORCH_CHECK(b.is_contiguous() && b.numel() == n && b.device() == like.device(), op, ": ", name, " must be bf16 [", n, "]");
+}
+static Tensor se_ws(const SeShape& g, const Tensor& u, int backward) {
+  return at::empty({std::max<int64_t>(1, tam::se_reduce_ws(g.N, g.P, g.C, backward))}, u.options().dtype(at::kFloat));
+}
+
+void se_policy_op(int64_t p) { tam::se_policy((int)p); }
+
+void se_squeeze_op(const Tensor& u, const Tensor& z) {
+  const char* op = "tam.se_squeeze";
+  const SeShape g = se_shape(u, op);
+  se_mat(z, g.N, g.C, u, "z", op);
+  Tensor ws = se_ws(g, u, 0);
+  tam::se_squeeze(bp(u), z.data_ptr<float>(), ws.data_ptr<float>(), g.N, g.P, g.C, cur_stream(u));
+}
+
+void se_excite_fwd_op(const Tensor& z, const Tensor& w1, const Tensor& b1, const Tensor& w2, const Tensor& b2,
+                      const Tensor& h, const Tensor& s) {
+  const char* op = "tam.se_excite_fwd";
+  const auto [N, C, Cr] = se_fc_shape(z, w1, w2, op);
+  se_bias(b1, Cr, z, "b1", op); se_bias(b2, C, z, "b2", op);
+  se_mat(h, N, Cr, z, "h", op); se_mat(s, N, C, z, "s", op);
+  tam::se_excite_fwd(z.data_ptr<float>(), bp(w1), bp(b1), bp(w2), bp(b2), h.data_ptr<float>(), s.data_ptr<float>(), N,
+                     C, Cr, cur_stream(z));
+}
+
+void se_gate_fwd_op(const Tensor& u, const Tensor& s, const optional<Tensor>& idn, const Tensor& y) {
+  const char* op = "tam.se_gate_fwd";
+  const SeShape g = se_shape(u, op);
+  se_mat(s, g.N, g.C, u, "s", op); se_like(y, u, "y", op);
+  if (idn.has_value() && idn->defined()) se_like(*idn, u, "idn", op);
+  tam::se_gate_fwd(bp(u), s.data_ptr<float>(), opt_ptr<const tam::bf16_t>(idn), bpm(y), g.N, g.P, g.C, cur_stream(u));
+}
+
+// g (bf16, u's shape) receives the masked gradient: the identity branch's
+void se_gate_bwd_reduce_op(const Tensor& dy, const optional<Tensor>& addend, const Tensor& y, const Tensor& u,
+                           const Tensor& g_out, const Tensor& ds) {
+  const char* op = "tam.se_gate_bwd_reduce";
+  const SeShape g = se_shape(u, op);
+  se_like(dy, u, "dy", op); se_like(y, u, "y", op); se_like(g_out, u, "g", op);
+  if (addend.has_value() && addend->defined()) se_like(*addend, u, "addend", op);
+  se_mat(ds, g.N, g.C, u, "ds", op);
+  Tensor ws = se_ws(g, u, 1);
+  tam::se_gate_bwd_reduce(bp(dy), opt_ptr<const tam::bf16_t>(addend), bp(y), bp(u), bpm(g_out), ds.data_ptr<float>(),
+                          ws.data_ptr<float>(), g.N, g.P, g.C, cur_stream(u));
+}
+
+// dw1 / db1 / dw2 / db2 (fp32) accumulate, like the conv weight gradients into
+// the optimizer-zeroed buffer; dz is stored
+void se_excite_bwd_op(const Tensor& ds, const Tensor& s, const Tensor& h, const Tensor& z, const Tensor& w1,
+                      const Tensor& w2, const Tensor& dw1, const Tensor& db1, const Tensor& dw2, const Tensor& db2,
+                      const Tensor& dz) {
+  const char* op = "tam.se_excite_bwd";
+  const auto [N, C, Cr] = se_fc_shape(z, w1, w2, op);
+  se_mat(ds, N, C, z, "ds", op); se_mat(s, N, C, z, "s", op); se_mat(h, N, Cr, z, "h", op); se_mat(dz, N, C, z, "dz", op);
+  se_mat(dw1, Cr, C, z, "dw1", op); se_mat(dw2, C, Cr, z, "dw2", op);
+  se_mat(db1, 1, Cr, z, "db1", op); se_mat(db2, 1, C, z, "db2", op);
+  Tensor dh = at::empty({N, Cr}, z.options());
+  tam::se_excite_bwd(ds.data_ptr<float>(), s.data_ptr<float>(), h.data_ptr<float>(), z.data_ptr<float>(), bp(w1),
+                     bp(w2), dh.data_ptr<float>(), dw1.data_ptr<float>(), db1.data_ptr<float>(),
+                     dw2.data_ptr<float>(), db2.data_ptr<float>(), dz.data_ptr<float>(), N, C, Cr, cur_stream(z));
+}
+
+void se_gate_bwd_apply_op(const Tensor& g_in, const Tensor& s, const Tensor& dz, const Tensor& du) {
+  const char* op = "tam.se_gate_bwd_apply";
+  const SeShape g = se_shape(g_in, op);
+  se_mat(s, g.N, g.C, g_in, "s", op); se_mat(dz, g.N, g.C, g_in, "dz", op); se_like(du, g_in, "du", op);
+  tam::se_gate_bwd_apply(bp(g_in), s.data_ptr<float>(), dz.data_ptr<float>(), bpm(du), g.N, g.P, g.C,
+                         cur_stream(g_in));
+}
+
 // the dropout arguments of the LN ops / dropout_apply: rec (optional int32
 // [4] {seed, stream, step, 0} on the data's device), site, thr = round(p *
 // 65536) in (0, 65536), scale = 65536 / (65536 - thr); no rec = no dropout
@@ -1841,6 +1954,13 @@ TORCH_LIBRARY(tam, m) {
   m.def("groupnorm_backward(Tensor dy, Tensor? y, Tensor x, Tensor mean, Tensor rstd, Tensor gamma, Tensor(a!) dx, Tensor(b!)? dres, Tensor(c!) cpart, Tensor(d!)? dgamma, Tensor(e!)? dbeta, int groups, bool relu, Tensor? addend=None) -> int", &groupnorm_backward_op);
   m.def("gn_policy(int policy) -> ()", &gn_policy_op);
   m.def("gn_resident_fits(int P, int C, int groups, bool backward) -> bool", &gn_resident_fits_op);
+  m.def("se_policy(int policy) -> ()", &se_policy_op);
+  m.def("se_squeeze(Tensor u, Tensor(a!) z) -> ()", &se_squeeze_op);
+  m.def("se_excite_fwd(Tensor z, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor(a!) h, Tensor(b!) s) -> ()", &se_excite_fwd_op);
+  m.def("se_gate_fwd(Tensor u, Tensor s, Tensor? idn, Tensor(a!) y) -> ()", &se_gate_fwd_op);
+  m.def("se_gate_bwd_reduce(Tensor dy, Tensor? addend, Tensor y, Tensor u, Tensor(a!) g, Tensor(b!) ds) -> ()", &se_gate_bwd_reduce_op);
+  m.def("se_excite_bwd(Tensor ds, Tensor s, Tensor h, Tensor z, Tensor w1, Tensor w2, Tensor(a!) dw1, Tensor(b!) db1, Tensor(c!) dw2, Tensor(d!) db2, Tensor(e!) dz) -> ()", &se_excite_bwd_op);
+  m.def("se_gate_bwd_apply(Tensor g, Tensor s, Tensor dz, Tensor(a!) du) -> ()", &se_gate_bwd_apply_op);
   m.def("col_reduce_acc(Tensor part, int nblk, int W, Tensor(a!) out0, Tensor(b!) out1, int split) -> ()", &col_reduce_acc_op);
   m.def("col_reduce_acc_batch(Tensor[] parts, int[] nblk, Tensor(a!)[] out0, Tensor(b!)[] out1) -> ()", &col_reduce_acc_batch_op);
   m.def("maxpool_forward(Tensor x, Tensor(a!) y, Tensor(b!) idx, int R, int S, int stride, int pad) -> ()", &maxpool_forward_op);

@@ -74,6 +74,36 @@ int gn_backward(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const b
                 const float* rstd, const float* gamma, int N, int P, int C, int G, int relu, bf16_t* dx,
                 bf16_t* dres, float* cpart, float* ws, hipStream_t s);
 
+// Squeeze-and-Excitation (se.hip): u, idn, y, dy, addend, g, du bf16 [N][P][C]
+// (NHWC, P = H * W); z, s, ds, dz fp32 [N][C]; h fp32 [N][Cr]; w1 [Cr][C],
+// b1 [Cr], w2 [C][Cr], b2 [C] bf16; C % 8 == 0, C <= 2048, Cr % 8 == 0, 8 <= Cr
+// <= 512, N <= 65535, P * C < 2^31 (checked by the caller). The two reductions
+// (se_squeeze, se_gate_bwd_reduce) run single-pass (a block per sample and
+// 64-channel slab) or tiled (SE_TILE-pixel tiles, partials in ws summed in tile
+// order), picked from P per kernel; ws: se_reduce_ws(N, P, C, backward) floats.
+constexpr int SE_TILE = 256;
+inline int se_tiles(int P) { return (P + SE_TILE - 1) / SE_TILE; }
+void se_policy(int p);   // 0 auto, 1 tiled, 2 single pass (A/B, tests)
+long se_reduce_ws(int N, int P, int C, int backward);
+// z = mean_p u
+void se_squeeze(const bf16_t* u, float* z, float* ws, int N, int P, int C, hipStream_t s);
+// h = relu(z w1^T + b1), sg = sigmoid(h w2^T + b2)
+void se_excite_fwd(const float* z, const bf16_t* w1, const bf16_t* b1, const bf16_t* w2, const bf16_t* b2, float* h,
+                   float* sg, int N, int C, int Cr, hipStream_t s);
+// y = relu(sg[n][c] * u (+ idn))
+void se_gate_fwd(const bf16_t* u, const float* sg, const bf16_t* idn, bf16_t* y, int N, int P, int C, hipStream_t s);
+// g = (dy (+ addend)) where y > 0, else 0; ds = sum_p g * u
+void se_gate_bwd_reduce(const bf16_t* dy, const bf16_t* addend, const bf16_t* y, const bf16_t* u, bf16_t* g,
+                        float* ds, float* ws, int N, int P, int C, hipStream_t s);
+// dt = ds sg (1 - sg); dw2 += dt^T h, db2 += sum_n dt; dh = (dt w2) (h > 0)
+// (scratch, fp32 [N][Cr]); dw1 += dh^T z, db1 += sum_n dh; dz = dh w1
+void se_excite_bwd(const float* ds, const float* sg, const float* h, const float* z, const bf16_t* w1,
+                   const bf16_t* w2, float* dh, float* dw1, float* db1, float* dw2, float* db2, float* dz, int N,
+                   int C, int Cr, hipStream_t s);
+// du = sg[n][c] * g + dz[n][c] / P
+void se_gate_bwd_apply(const bf16_t* g, const float* sg, const float* dz, bf16_t* du, int N, int P, int C,
+                       hipStream_t s);
+
 // LayerNorm over last dim D (D % 8 == 0, D <= 2048)
 // addend (optional): LN of (x + addend), the bf16 sum also stored to sum_out
 // (a residual add fused into the next pre-LN)

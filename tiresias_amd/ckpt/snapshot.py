@@ -167,11 +167,12 @@ def load_snapshot(path: str, trainer) -> int:
         # is refused before anything is written: neither a silent cast nor a
         # reinterpretation of its bytes. A snapshot of another cardinality
         # (Trainer cardinality: other bottleneck widths) has another arena size
-        # and is refused here too
+        # and is refused here too, and so has one of another se_ratio (Trainer
+        # se_ratio: other or no SE parameters)
         if k in st and (v.dtype != st[k].dtype or v.numel() != st[k].numel()):
             raise ValueError(f"snapshot {path}: buffer {k!r} is {v.dtype} x {v.numel()}, the trainer holds "
                              f"{st[k].dtype} x {st[k].numel()} (a snapshot restores only into a trainer of "
-                             "the same model, cardinality and opt_dtype)")
+                             "the same model, cardinality, se_ratio and opt_dtype)")
     for k, v in d["state"].items():
         if k in st:
             st[k].copy_(v, non_blocking=False)

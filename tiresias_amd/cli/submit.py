@@ -11,6 +11,7 @@ Examples::
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --gpus 4 --iterations 800 --trust-ratio 0.001
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --batch 4 --iterations 800 --norm group
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --iterations 800 --cardinality 32
+    python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --iterations 800 --se-ratio 16
     python -m tiresias_amd.cli.submit --spool /tmp/tam --status
     python -m tiresias_amd.cli.submit --spool /tmp/tam --shutdown
 """
@@ -56,6 +57,11 @@ def main(argv=None) -> int:
     ap.add_argument("--cardinality", type=int, metavar="G",
                     help="ResNeXt variant of a ResNet job: every bottleneck's 3x3 conv runs in G groups (a multiple "
                          "of 4 in [4, 64]; resnet50 with 32 is ResNeXt-50 32x4d); other models reject it")
+    ap.add_argument("--se-ratio", type=int, metavar="R",
+                    help="Squeeze-and-Excitation variant of a ResNet job: every bottleneck gates its output per "
+                         "(sample, channel) through two FCs C -> max(8, C / R) -> C (R in 4, 8, 16, 32; resnet50 "
+                         "with 16 is SE-ResNet-50, with --cardinality 32 SE-ResNeXt-50 32x4d); other models "
+                         "reject it")
     ap.add_argument("--status", action="store_true")
     ap.add_argument("--shutdown", action="store_true", help="stop serving once the cluster drains")
     a = ap.parse_args(argv)
@@ -72,7 +78,7 @@ def main(argv=None) -> int:
     jid = sp.submit(a.model, a.gpus, iterations=a.iterations, duration=a.duration, job_id=a.job_id,
                     batch=a.batch, grad_clip=a.grad_clip, dropout=a.dropout,
                     attn_dropout=a.attn_dropout, opt_dtype=a.opt_dtype, trust_ratio=a.trust_ratio,
-                    norm=a.norm, cardinality=a.cardinality)
+                    norm=a.norm, cardinality=a.cardinality, se_ratio=a.se_ratio)
     print(jid)
     return 0
 

@@ -153,6 +153,7 @@ class ReplayJob:
     trust_ratio: Optional[float] = None  # layer-wise trust coefficient of the job: LARS / LAMB (None = off)
     norm: Optional[str] = None           # normalisation of a CNN job: "batch" / "group" (None = batch)
     cardinality: Optional[int] = None    # ResNeXt cardinality of a ResNet job (None = the plain model)
+    se_ratio: Optional[int] = None       # Squeeze-and-Excitation ratio of a ResNet job (None = no SE blocks)
 
 
 class Controller:
@@ -517,6 +518,7 @@ class Controller:
                 jid, model, g, iters, batch, clip, drop, adrop, odt, eta = self._validate(req)
                 norm = self._validate_norm(req, model)
                 card = self._validate_cardinality(req, model)
+                se = self._validate_se_ratio(req, model)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -530,7 +532,7 @@ class Controller:
                            num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
                                         dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta,
-                                        norm=norm, cardinality=card)
+                                        norm=norm, cardinality=card, se_ratio=se)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -634,6 +636,15 @@ class Controller:
 
         return check_cardinality(model, req.get("cardinality"))
 
+    @staticmethod
+    def _validate_se_ratio(req: dict, model: str) -> Optional[int]:
+        """The request's ``se_ratio`` key (absent / null: None, no SE blocks);
+        ValueError for a value that is not one or a model without a
+        bottleneck to gate."""
+        from .trainer import check_se_ratio
+
+        return check_se_ratio(model, req.get("se_ratio"))
+
     def status(self) -> dict:
         s = self.sched
         jobs = {}
@@ -700,6 +711,8 @@ class Controller:
                     act["norm"] = rj.norm
                 if rj.cardinality is not None:
                     act["cardinality"] = rj.cardinality
+                if rj.se_ratio is not None:
+                    act["se_ratio"] = rj.se_ratio
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
                     act["source"] = "snapshot"
@@ -942,13 +955,16 @@ class Worker:
         fp32-state job, nor the reverse), so a bf16- or factored-state job's key carries it;
         the per-job setters (clip, dropouts, trust ratio) are not part of the key.
         A GroupNorm job's model has other layers and no running statistics, so
-        its key carries ``norm`` too, and a ResNeXt job's its ``cardinality``."""
+        its key carries ``norm`` too, a ResNeXt job's its ``cardinality`` and an
+        SE job's its ``se_ratio``."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
         if act.get("opt_dtype") in ("bf16", "factored"):
             key += (act["opt_dtype"],)
         if act.get("norm") == "group":
             key += ("norm=group",)
-        return key + (f"cardinality={act['cardinality']}",) if act.get("cardinality") is not None else key
+        if act.get("cardinality") is not None:
+            key += (f"cardinality={act['cardinality']}",)
+        return key + (f"se_ratio={act['se_ratio']}",) if act.get("se_ratio") is not None else key
 
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
@@ -976,6 +992,9 @@ class Worker:
             if free[-1].cardinality != act.get("cardinality"):
                 raise RuntimeError(f"warm pool {key}: a cardinality={free[-1].cardinality} trainer is pooled under "
                                    f"the key of a cardinality={act.get('cardinality')} job")
+            if free[-1].se_ratio != act.get("se_ratio"):
+                raise RuntimeError(f"warm pool {key}: a se_ratio={free[-1].se_ratio} trainer is pooled under "
+                                   f"the key of a se_ratio={act.get('se_ratio')} job")
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
@@ -991,7 +1010,7 @@ class Worker:
                     ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
                     attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"),
                     trust_ratio=act.get("trust_ratio"), norm=act.get("norm"),
-                    cardinality=act.get("cardinality"))
+                    cardinality=act.get("cardinality"), se_ratio=act.get("se_ratio"))
         t.pool_key = key
         return t
 
@@ -1332,7 +1351,7 @@ class Worker:
                     t.rebind(self._group(ranks))
                     # (the trainer's own state format, whatever the action carries)
                     t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype, norm=t.norm,
-                                                        cardinality=t.cardinality))
+                                                        cardinality=t.cardinality, se_ratio=t.se_ratio))
                 elif self.rank in ranks:
                     self._bind(self.trainers[a["job"]], ranks)
                 if self.rank in ranks and "step" in a:

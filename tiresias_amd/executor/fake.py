@@ -87,6 +87,7 @@ class FakeCluster:
         self.odt: Dict[str, Optional[str]] = {}      # job -> optimizer-state format (start action's opt_dtype)
         self.norm: Dict[str, Optional[str]] = {}     # job -> normalisation it was started with (start action's norm)
         self.card: Dict[str, Optional[int]] = {}     # job -> ResNeXt cardinality it was started with
+        self.se: Dict[str, Optional[int]] = {}       # job -> Squeeze-and-Excitation ratio it was started with
         self.groups: Set[Tuple[int, ...]] = set()
         self.stats = {"p2p_bytes": 0.0, "spill_bytes": 0.0, "restore_bytes": 0.0, "starts": 0,
                       "resident_resumes": 0, "rounds": 0}
@@ -193,6 +194,14 @@ class FakeCluster:
                     raise ProtocolError(f"start of {job} with cardinality {card!r}, its state was built with "
                                         f"{self.card.get(job)!r}")
                 self.card[job] = card
+                # and so does se_ratio
+                se = a.get("se_ratio")
+                if se is not None and (isinstance(se, bool) or not isinstance(se, int) or se not in (4, 8, 16, 32)):
+                    raise ProtocolError(f"start of {job} with se_ratio {se!r}")
+                if job in self.held and self.se.get(job) != se:
+                    raise ProtocolError(f"start of {job} with se_ratio {se!r}, its state was built with "
+                                        f"{self.se.get(job)!r}")
+                self.se[job] = se
                 src = a["source"]
                 b = _state_bytes(a["model"], a.get("opt_dtype"))
                 if src == "fresh":

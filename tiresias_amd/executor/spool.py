@@ -23,7 +23,8 @@ Request schema (JSON)::
 
 A job that asks for ``--norm`` carries one more key, ``"norm": "batch" |
 "group"`` (ResNet models); a request without it is written as before. The
-same holds for ``--cardinality``: ``"cardinality": G`` (ResNeXt, ResNet models).
+same holds for ``--cardinality``: ``"cardinality": G`` (ResNeXt, ResNet models)
+and for ``--se-ratio``: ``"se_ratio": R`` (Squeeze-and-Excitation, ResNet models).
 """
 from __future__ import annotations
 
@@ -53,7 +54,8 @@ class Spool:
                batch: Optional[int] = None, grad_clip: Optional[float] = None,
                dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
                opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
-               norm: Optional[str] = None, cardinality: Optional[int] = None) -> str:
+               norm: Optional[str] = None, cardinality: Optional[int] = None,
+               se_ratio: Optional[int] = None) -> str:
         if iterations is None and duration is None:
             raise ValueError("give iterations or duration")
         jid = job_id or f"sub-{time.time_ns()}-{os.getpid()}"
@@ -65,6 +67,8 @@ class Spool:
             req["norm"] = norm
         if cardinality is not None:
             req["cardinality"] = cardinality
+        if se_ratio is not None:
+            req["se_ratio"] = se_ratio
         _atomic_write(os.path.join(self.root, "incoming", f"{jid}.json"), req)
         return jid
 

@@ -30,7 +30,8 @@ class Trainer:
                  ddp_shard: bool = False, ddp_wire: str = "fp32", grad_clip: Optional[float] = None,
                  dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
                  opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
-                 norm: Optional[str] = None, cardinality: Optional[int] = None):
+                 norm: Optional[str] = None, cardinality: Optional[int] = None,
+                 se_ratio: Optional[int] = None):
         self.model_name = model
         self.spec = MODELS[model]
         # normalisation of a CNN job (README "GroupNorm"): "group" builds the
@@ -43,6 +44,10 @@ class Trainer:
         # norm it fixes the model's structure: set at construction, part of
         # the worker's warm-pool key, no per-job setter
         self.cardinality = check_cardinality(model, self.spec.cardinality if cardinality is None else cardinality)
+        # Squeeze-and-Excitation ratio of a ResNet job (README "SE blocks"): r
+        # adds an SE block (four parameters, the se.hip kernels) to every
+        # bottleneck. Structure again: construction, pool key, no setter
+        self.se_ratio = check_se_ratio(model, self.spec.se_ratio if se_ratio is None else se_ratio)
         if opt_dtype is None:
             opt_dtype = self.spec.opt_dtype
         if opt_dtype not in (None, "fp32", "bf16", "factored"):
@@ -92,6 +97,8 @@ class Trainer:
             mk["norm"] = "group"
         if self.cardinality is not None:
             mk["cardinality"] = self.cardinality
+        if self.se_ratio is not None:
+            mk["se_ratio"] = self.se_ratio
         self.model = make_model(model, self.arena, **mk)
         self.arena.materialize()
         n = self.arena.numel
@@ -978,6 +985,21 @@ def check_cardinality(model: str, v) -> Optional[int]:
     check_cardinality_value(v)
     if not getattr(MODELS[model].builder, "cardinalities", False):
         raise ValueError(f"cardinality={v!r}: {model!r} has no bottleneck 3x3 conv to group (the knob is for the "
+                         "ResNet models)")
+    return v
+
+
+def check_se_ratio(model: str, v) -> Optional[int]:
+    """The Squeeze-and-Excitation ratio a job of ``model`` runs with (None: no
+    SE blocks); ValueError for a value that is not one of the integers 4, 8,
+    16, 32, or for a model whose builder has no bottleneck to gate."""
+    if v is None:
+        return None
+    from ..models.cnn import check_se_ratio_value
+
+    check_se_ratio_value(v)
+    if not getattr(MODELS[model].builder, "se_ratios", False):
+        raise ValueError(f"se_ratio={v!r}: {model!r} has no bottleneck to put an SE block on (the knob is for the "
                          "ResNet models)")
     return v
 

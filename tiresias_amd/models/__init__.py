@@ -68,6 +68,10 @@ class ModelSpec:
     # None keeps the plain bottleneck, G builds it with a G-group 3x3 conv
     # (ResNet models; others reject it). No shipped model sets it
     cardinality: Optional[int] = None
+    # Squeeze-and-Excitation reduction ratio of a ResNet job (Trainer se_ratio,
+    # --se-ratio): None keeps the plain bottleneck, r in {4, 8, 16, 32} adds an
+    # SE block to each (ResNet models; others reject it). No shipped model sets it
+    se_ratio: Optional[int] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

@@ -45,15 +45,25 @@ def check_cardinality_value(v) -> None:
         raise ValueError(f"cardinality must be an integer multiple of 4 in [4, 64], got {v!r}")
 
 
+def check_se_ratio_value(v) -> None:
+    """ValueError unless ``v`` is None or a Squeeze-and-Excitation reduction
+    ratio: one of the integers 4, 8, 16, 32."""
+    if v is None:
+        return
+    if isinstance(v, bool) or not isinstance(v, int) or v not in (4, 8, 16, 32):
+        raise ValueError(f"se_ratio must be one of 4, 8, 16, 32, got {v!r}")
+
+
 class ResNet50:
     """torchvision-style ResNet-50 v1.5 (stride on the 3x3 conv), NHWC."""
 
     name = "resnet50"
     norms = ("batch", "group")     # what Trainer(norm=) / submit --norm may ask of this model
     cardinalities = True           # Trainer(cardinality=) / submit --cardinality: the ResNeXt variant
+    se_ratios = True               # Trainer(se_ratio=) / submit --se-ratio: Squeeze-and-Excitation blocks
 
     def __init__(self, arena: Arena, num_classes: int = 1000, layers=(3, 4, 6, 3), width: int = 64,
-                 in_ch: int = 8, norm: str = "batch", cardinality=None, group_width: int = 4):
+                 in_ch: int = 8, norm: str = "batch", cardinality=None, group_width: int = 4, se_ratio=None):
         if norm not in ("batch", "group"):
             raise ValueError(f"norm must be 'batch' or 'group', got {norm!r}")
         check_cardinality_value(cardinality)
@@ -61,6 +71,11 @@ class ResNet50:
         # G * group_width * 2^i, its 3x3 conv has G groups (Fx.conv2d groups=);
         # None: the plain ResNet, same parameters and arena order as ever
         self.cardinality = cardinality
+        check_se_ratio_value(se_ratio)
+        # se_ratio r (SE-ResNet, Hu et al. 2018): every bottleneck gates its bn3
+        # output per (sample, channel) before the residual add (Fx.se_block),
+        # through two FCs C -> max(8, C // r) -> C; None: no such parameters
+        self.se_ratio = se_ratio
         self.arena = arena
         dev = arena.device
         self.training = True
@@ -98,6 +113,12 @@ class ResNet50:
                     blk["down_bn"] = (A.add(pre + ".dbn.g", (w * 4,), init="ones", decay=False, fp32_compute=True),
                                       A.add(pre + ".dbn.b", (w * 4,), init="zeros", decay=False, fp32_compute=True))
                     self.bn_state[pre + ".dbn"] = _BNState(w * 4, dev)
+                if se_ratio is not None:
+                    cr = max(8, w * 4 // se_ratio)
+                    blk["se"] = (A.add(pre + ".se.w1", (cr, w * 4), init="kaiming"),
+                                 A.add(pre + ".se.b1", (cr,), init="zeros", decay=False),
+                                 A.add(pre + ".se.w2", (w * 4, cr), init="kaiming"),
+                                 A.add(pre + ".se.b2", (w * 4,), init="zeros", decay=False))
                 blk["pre"] = pre
                 self.blocks.append(blk)
                 cin = w * 4
@@ -182,7 +203,11 @@ class ResNet50:
                 idn = Fx.conv2d(y2, blk["down"], stride=blk["stride"],
                                 bn_stats=self._st(pre + ".dbn"))
                 idn = self._bn(idn, blk["down_bn"], pre + ".dbn", relu=False)
-            y = self._bn(o, blk["bn3"], pre + ".bn3", relu=True, res=idn)
+            if "se" in blk:
+                o = self._bn(o, blk["bn3"], pre + ".bn3", relu=False)
+                y = Fx.se_block(o, idn, *blk["se"])
+            else:
+                y = self._bn(o, blk["bn3"], pre + ".bn3", relu=True, res=idn)
         y = Fx.global_avgpool(y)
         return Fx.linear(y, self.fc_w, self.fc_b)
 

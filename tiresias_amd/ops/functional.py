@@ -944,6 +944,98 @@ def groupnorm(x: torch.Tensor, g: Param, b: Param, groups: int, relu: bool = Fal
     return y
 
 
+# ============================================================ Squeeze-and-Excitation
+# The SE block of a bottleneck (csrc/kernels/se.hip): squeeze, two FCs, gate +
+# residual add + ReLU, one autograd node around six kernels. Its output is a
+# residual-tap producer like a BN output (GradSlot / addend); the four
+# parameter gradients accumulate into the optimizer-zeroed buffer.
+class _SE(Function):
+    @staticmethod
+    def forward(ctx, u, idn, token, w1: Param, b1: Param, w2: Param, b2: Param,
+                slot: Optional[GradSlot] = None):
+        N, C = u.shape[0], u.shape[-1]
+        Cr = w1.shape[0]
+        if u.is_cuda:
+            z = torch.empty(N, C, dtype=torch.float32, device=u.device)
+            h = torch.empty(N, Cr, dtype=torch.float32, device=u.device)
+            s = torch.empty_like(z)
+            y = torch.empty_like(u)
+            _T().se_squeeze(u, z)
+            _T().se_excite_fwd(z, w1.w, b1.w, w2.w, b2.w, h, s)
+            _T().se_gate_fwd(u, s, idn, y)
+        else:
+            uf = u.float().reshape(N, -1, C)
+            z = uf.mean(1)
+            h = (z @ w1.w.float().t() + b1.w.float()).clamp_min(0)
+            s = torch.sigmoid(h @ w2.w.float().t() + b2.w.float())
+            yf = s[:, None, :] * uf
+            if idn is not None:
+                yf = yf + idn.float().reshape(N, -1, C)
+            y = yf.clamp_min(0).reshape(u.shape).to(BF16)
+        ctx.p, ctx.has_idn, ctx.slot = (w1, b1, w2, b2), idn is not None, slot
+        ctx.save_for_backward(u, y, z, h, s)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, y, z, h, s = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.p
+        dy = dy.contiguous()
+        N, C = u.shape[0], u.shape[-1]
+        add = None
+        if ctx.slot is not None:
+            add, ctx.slot.stash = ctx.slot.stash, None
+        for p in ctx.p:
+            p.gw_epoch = p.arena.grad_epoch       # written (accumulated) this step: see grad_mode
+        if dy.is_cuda:
+            g = torch.empty_like(u)
+            ds = torch.empty_like(s)
+            _T().se_gate_bwd_reduce(dy, add, y, u, g, ds)
+            dz = torch.empty_like(s)
+            _T().se_excite_bwd(ds, s, h, z, w1.w, w2.w, w1.grad, b1.grad, w2.grad, b2.grad, dz)
+            du = torch.empty_like(u)
+            _T().se_gate_bwd_apply(g, s, dz, du)
+        else:
+            gf = dy.float().reshape(N, -1, C)
+            if add is not None:
+                gf = gf + add.float().reshape(N, -1, C)
+            gf = gf * (y.float().reshape(N, -1, C) > 0)
+            uf = u.float().reshape(N, -1, C)
+            dt = (gf * uf).sum(1) * s * (1 - s)
+            dh = (dt @ w2.w.float()) * (h > 0)
+            w2.grad += dt.t() @ h
+            b2.grad += dt.sum(0)
+            w1.grad += dh.t() @ z
+            b1.grad += dh.sum(0)
+            dz = dh @ w1.w.float()
+            du = (s[:, None, :] * gf + dz[:, None, :] / uf.shape[1]).reshape(u.shape).to(BF16)
+            g = gf.reshape(u.shape).to(BF16)
+        for p in ctx.p:
+            p.grad_ready()
+        return du, (g if ctx.has_idn else None), None, None, None, None, None, None
+
+
+def se_block(u: torch.Tensor, idn: Optional[torch.Tensor], w1: Param, b1: Param, w2: Param,
+             b2: Param) -> torch.Tensor:
+    """y = relu(s * u + idn) with s = sigmoid(relu(mean_hw(u) W1^T + b1) W2^T + b2)
+    per (sample, channel) of an NHWC tensor: the Squeeze-and-Excitation block
+    with the bottleneck's residual add and ReLU. w1 [Cr, C], w2 [C, Cr];
+    C % 8 == 0, C <= 2048, Cr % 8 == 0, 8 <= Cr <= 512; anything else raises."""
+    C, Cr = u.shape[-1], w1.shape[0]
+    if C % 8 or C > 2048 or Cr % 8 or not 8 <= Cr <= 512 or w1.shape != (Cr, C) or w2.shape != (C, Cr):
+        raise ValueError(f"se_block: C = {C}, w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)}: needs C % 8 == 0, "
+                         "C <= 2048, Cr % 8 == 0, 8 <= Cr <= 512, w1 [Cr, C] and w2 [C, Cr]")
+    if not u.is_contiguous():
+        u = u.contiguous()
+    if idn is not None and not idn.is_contiguous():
+        idn = idn.contiguous()
+    slot = GradSlot() if (u.is_cuda and torch.is_grad_enabled()) else None
+    y = _SE.apply(u, idn, w1.arena.token, w1, b1, w2, b2, slot)
+    if slot is not None:
+        y._tam_slot = slot
+    return y
+
+
 # ============================================================ dropout
 # Training dropout without stored masks: the mask of a dropout call is a pure
 # function of the trainer's dropout record (int32[4] {seed, stream, step, 0},
