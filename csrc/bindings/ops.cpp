@@ -1764,9 +1764,21 @@ static tam::LnDrop attn_drop_args(const optional<Tensor>& rec, int64_t site, int
   d.scale = (float)scale;
   return d;
 }
+// the rotary table: fp32 [n][2][32] (cos row, sin row), contiguous, on the
+// inputs' device, a row for every query and key index the kernels rotate
+static const float* attn_rope_arg(const optional<Tensor>& rope, const Tensor& q, const Tensor& k, const char* op) {
+  if (!(rope.has_value() && rope->defined())) return nullptr;
+  TORCH_CHECK(rope->scalar_type() == at::kFloat && rope->is_contiguous() && rope->device() == q.device(), op,
+              ": rope must be a contiguous fp32 tensor on the data's device");
+  TORCH_CHECK(rope->dim() == 3 && rope->size(1) == 2 && rope->size(2) == 32, op, ": rope must be [n, 2, 32]");
+  TORCH_CHECK(rope->size(0) >= std::max(q.size(1), k.size(1)), op, ": rope has ", rope->size(0),
+              " rows, needs max(Sq, Sk) = ", std::max(q.size(1), k.size(1)));
+  return rope->data_ptr<float>();
+}
 void attn_forward_op(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                      const Tensor& lse, bool causal, double scale, const optional<Tensor>& kv_len,
-                     const optional<Tensor>& drop_rec, int64_t drop_site, int64_t drop_thr, double drop_scale) {
+                     const optional<Tensor>& drop_rec, int64_t drop_site, int64_t drop_thr, double drop_scale,
+                     const optional<Tensor>& rope) {
   check_attn_view(q, "q"); check_attn_view(k, "k"); check_attn_view(v, "v"); check_attn_view(o, "o");
   TORCH_CHECK(k.stride(1) == v.stride(1), "tam.attn: k/v token strides differ");
   check_f32(lse, "lse");
@@ -1776,13 +1788,14 @@ void attn_forward_op(const Tensor& q, const Tensor& k, const Tensor& v, const Te
   const tam::LnDrop drop = attn_drop_args(drop_rec, drop_site, drop_thr, drop_scale, q, k, "tam.attn_forward");
   tam::attn_forward(bp(q), bp(k), bp(v), bpm(o), lse.data_ptr<float>(), B, H, Sq, Sk, q.stride(1),
                     k.stride(1), o.stride(1), q.stride(0), k.stride(0), o.stride(0), causal, (float)scale,
-                    opt_ptr<const int>(kv_len), cur_stream(q), drop);
+                    opt_ptr<const int>(kv_len), cur_stream(q), drop,
+                    attn_rope_arg(rope, q, k, "tam.attn_forward"));
 }
 void attn_backward_op(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o,
                       const Tensor& dout, const Tensor& lse, const Tensor& dq, const Tensor& dk,
                       const Tensor& dv, const Tensor& dq_acc, const Tensor& delta, bool causal,
                       double scale, const optional<Tensor>& kv_len, const optional<Tensor>& drop_rec,
-                      int64_t drop_site, int64_t drop_thr, double drop_scale) {
+                      int64_t drop_site, int64_t drop_thr, double drop_scale, const optional<Tensor>& rope) {
   check_attn_view(q, "q"); check_attn_view(k, "k"); check_attn_view(v, "v"); check_attn_view(o, "o");
   check_attn_view(dout, "dout"); check_attn_view(dq, "dq"); check_attn_view(dk, "dk");
   check_attn_view(dv, "dv");
@@ -1800,7 +1813,8 @@ void attn_backward_op(const Tensor& q, const Tensor& k, const Tensor& v, const T
                      bpm(dv), dq_acc.data_ptr<float>(), delta.data_ptr<float>(), B, H, Sq, Sk,
                      q.stride(1), k.stride(1), o.stride(1), q.stride(0), k.stride(0), o.stride(0), causal,
                      (float)scale,
-                     opt_ptr<const int>(kv_len), cur_stream(q), drop);
+                     opt_ptr<const int>(kv_len), cur_stream(q), drop,
+                     attn_rope_arg(rope, q, k, "tam.attn_backward"));
 }
 
 // ------------------------------------------------------------------ LSTM
@@ -2017,8 +2031,8 @@ TORCH_LIBRARY(tam, m) {
   m.def("adafactor_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) state, Tensor(d!) fac, Tensor(e!) wb, float lr, float wd, int step, float gscale, Tensor params, Tensor tiles, Tensor tasks, Tensor(f!) partials, Tensor(g!) tslots, Tensor(h!) urms, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adafactor_op);
   m.def("adafactor_tile() -> int[]", &adafactor_tile_op);
   m.def("lstm_guard_step(Tensor(a!) err) -> ()", &lstm_guard_step_op);
-  m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_forward_op);
-  m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0) -> ()", &attn_backward_op);
+  m.def("attn_forward(Tensor q, Tensor k, Tensor v, Tensor(a!) o, Tensor(b!) lse, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0, Tensor? rope=None) -> ()", &attn_forward_op);
+  m.def("attn_backward(Tensor q, Tensor k, Tensor v, Tensor o, Tensor dout, Tensor lse, Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor(d!) dq_acc, Tensor(e!) delta, bool causal, float scale, Tensor? kv_len, Tensor? drop_rec=None, int drop_site=0, int drop_thr=0, float drop_scale=1.0, Tensor? rope=None) -> ()", &attn_backward_op);
   m.def("lstm_step_forward(Tensor gx, Tensor w_hh, Tensor? h_prev, Tensor? c_prev, Tensor(a!) c_out, Tensor(b!) h_out, Tensor(c!) act) -> ()", &lstm_step_fwd_op);
   m.def("lstm_seq_forward(Tensor gx, Tensor w_hh, Tensor(a!) hs, Tensor(b!) cs, Tensor(c!) act, bool reverse, Tensor(d!) sync, Tensor(e!)? job_err=None, int grids=-1, int reserved_cus=0, bool zeroed=False) -> bool", &lstm_seq_fwd_op);
   m.def("lstm_seq_backward(Tensor act, Tensor cs, Tensor dH, Tensor w_hh, Tensor(a!) dG, bool reverse, Tensor(b!) sync, Tensor(c!)? job_err=None, int grids=-1, int reserved_cus=0, bool zeroed=False) -> bool", &lstm_seq_bwd_op);

@@ -263,16 +263,20 @@ void adafactor_step(float* w, float* g, float* state, float* fac, bf16_t* wb, lo
 // with the LSE of the undropped scores; site is the attention call's ordinal,
 // thr = round(p * 256) in (0, 256), scale = 256 / (256 - thr); mask contract
 // in tam/philox.h. The backward regenerates the mask from the same arguments.
+// rope (!= nullptr): rotary position embedding of q and k inside the kernels,
+// pairs (j, j + 32), angle = token index * 10000^(-j/32), from a constant fp32
+// table [n][2][32] (cos row, sin row; n >= max(Sq, Sk)); the backward returns
+// dq, dk with respect to the unrotated inputs. v is not rotated.
 void attn_forward(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, int B,
                   int H, int Sq, int Sk, long q_stride, long kv_stride, long o_stride, long q_bstride,
                   long kv_bstride, long o_bstride, int causal, float scale, const int* kv_len, hipStream_t s,
-                  LnDrop drop = {});
+                  LnDrop drop = {}, const float* rope = nullptr);
 void attn_short_policy(int p);   // 1: Sk <= 128 backward in one fused launch (default)
 void attn_backward(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o,
                    const bf16_t* dout, const float* lse, bf16_t* dq, bf16_t* dk, bf16_t* dv,
                    float* dq_acc, float* delta, int B, int H, int Sq, int Sk, long q_stride,
                    long kv_stride, long o_stride, long q_bstride, long kv_bstride, long o_bstride, int causal,
-                   float scale, const int* kv_len, hipStream_t s, LnDrop drop = {});
+                   float scale, const int* kv_len, hipStream_t s, LnDrop drop = {}, const float* rope = nullptr);
 
 // LSTM cell pointwise (gates = x W_ih^T + h W_hh^T + b precomputed, fp32)
 void lstm_cell_forward(const float* gates, const float* c_prev, float* c_out, bf16_t* h_out,

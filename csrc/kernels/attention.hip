@@ -23,6 +23,19 @@
 // (16 v_mov_dpp per tile against three more 10-round Philox calls, ~100 VALU
 // ops each with quarter-rate 32-bit multiplies). The mask is regenerated in the
 // backward, nothing is stored. DROP = false is the kernel as it was.
+//
+// ROPE (all three kernels and the dQ cast): rotary position embedding of Q and K
+// (rotate-half pairing (j, j + 32), angle = token index * 10000^(-j/32)) from a
+// constant fp32 table [n][2][32] (cos row, sin row): no trigonometry here. Both
+// elements of a pair always sit in ONE lane -- the register fragments hold d =
+// 8g + j and 32 + 8g + j, the LDS tiles are fetched by a pair mapping (4
+// threads per row, chunks c and c + 4), the dK^T accumulators mt / mt + 2 hold
+// d and d + 32, and the short backward's dQ columns are re-dealt so nt = 0 / 1
+// do -- so every rotation is in-lane fp32 math on the way in (rounded to bf16
+// once: those values are the MFMA operands) and the transposed rotation on the
+// way out (dq, dk; fp32, before the bf16 store). V, dO, the softmax, the LSE and
+// the dropout mask indices are untouched. Zero-filled rows past Sq / Sk are not
+// rotated and read no table row. ROPE = false is the kernel as it was.
 #include "tam/common.h"
 #include "tam/igemm.h"
 #include "tam/kernels.h"
@@ -70,6 +83,85 @@ __device__ __forceinline__ void tile_store_mn(char* t, const uint4 (&r)[2], int 
     if (perm) row = rho(row);
     *(uint4*)(t + mnmaj_off<64>(row, 2 * (tid & 7))) = r[i];
   }
+}
+
+// ---- ROPE helpers. Table row p: cos(p w_j), j = 0..31, then sin(p w_j).
+// cs = {cos[j0..j0+7], sin[j0..j0+7]}: two 32-B runs of row p
+__device__ __forceinline__ void rope_load8(const float* __restrict__ rope, int p, int j0, float (&cs)[16]) {
+  const float4* t = (const float4*)(rope + (long)p * 64 + j0);
+  const float4 c0 = t[0], c1 = t[1], s0 = t[8], s1 = t[9];
+  cs[0] = c0.x; cs[1] = c0.y; cs[2] = c0.z; cs[3] = c0.w;
+  cs[4] = c1.x; cs[5] = c1.y; cs[6] = c1.z; cs[7] = c1.w;
+  cs[8] = s0.x; cs[9] = s0.y; cs[10] = s0.z; cs[11] = s0.w;
+  cs[12] = s1.x; cs[13] = s1.y; cs[14] = s1.z; cs[15] = s1.w;
+}
+// lo = x[j0..j0+7], hi = x[32+j0..32+j0+7] (bf16): x'_j = x_j cos - x_{j+32} sin,
+// x'_{j+32} = x_{j+32} cos + x_j sin, in fp32, rounded to bf16 once
+__device__ __forceinline__ void rope_rot8(uint4& lo, uint4& hi, const float (&cs)[16]) {
+  const uint32_t a[4] = {lo.x, lo.y, lo.z, lo.w}, b[4] = {hi.x, hi.y, hi.z, hi.w};
+  uint32_t ra[4], rb[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float a0 = __uint_as_float(a[e] << 16), a1 = __uint_as_float(a[e] & 0xffff0000u);
+    const float b0 = __uint_as_float(b[e] << 16), b1 = __uint_as_float(b[e] & 0xffff0000u);
+    const float c0 = cs[2 * e], c1 = cs[2 * e + 1], s0 = cs[8 + 2 * e], s1 = cs[8 + 2 * e + 1];
+    ra[e] = pack_bf2(a0 * c0 - b0 * s0, a1 * c1 - b1 * s1);
+    rb[e] = pack_bf2(b0 * c0 + a0 * s0, b1 * c1 + a1 * s1);
+  }
+  lo = make_uint4(ra[0], ra[1], ra[2], ra[3]);
+  hi = make_uint4(rb[0], rb[1], rb[2], rb[3]);
+}
+// a lane's Q / K fragment pair f[0] (d = 8g + j) / f[1] (d = 32 + 8g + j) of token p
+__device__ __forceinline__ void rope_rot_frag(s16x8_t (&f)[2], const float* __restrict__ rope, int p, int g) {
+  float cs[16];
+  rope_load8(rope, p, 8 * g, cs);
+  uint4 lo = __builtin_bit_cast(uint4, f[0]), hi = __builtin_bit_cast(uint4, f[1]);
+  rope_rot8(lo, hi, cs);
+  f[0] = __builtin_bit_cast(s16x8_t, lo);
+  f[1] = __builtin_bit_cast(s16x8_t, hi);
+}
+// the transposed rotation of an accumulator pair: a = dx'[j0..j0+3], b = dx'[32+j0..],
+// dx_j = dx'_j cos + dx'_{j+32} sin, dx_{j+32} = dx'_{j+32} cos - dx'_j sin
+__device__ __forceinline__ void rope_inv4(f32x4_t& a, f32x4_t& b, const float* __restrict__ rope, int p, int j0) {
+  const float4 c = *(const float4*)(rope + (long)p * 64 + j0);
+  const float4 s = *(const float4*)(rope + (long)p * 64 + 32 + j0);
+  const float cv[4] = {c.x, c.y, c.z, c.w}, sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float x = a[r], y = b[r];
+    a[r] = x * cv[r] + y * sv[r];
+    b[r] = y * cv[r] - x * sv[r];
+  }
+}
+// Pair-fetch mapping of a 64x64 tile for the rotated images (256 threads, still
+// 2 x 16 B each): thread (row = tid >> 2, c = tid & 3) loads chunks c and c + 4
+// of its row -- d = 8c.. and 32 + 8c.., the two halves of eight pairs -- and
+// that row's eight cos / sin. Rows past nrows are zero and read no table row
+// (cs = 0: the rotation keeps them zero).
+__device__ __forceinline__ void pair_fetch(const bf16_t* base, long stride, int row0, int nrows,
+                                           const float* __restrict__ rope, uint4 (&r)[2], float (&cs)[16],
+                                           int tid) {
+  const int gr = row0 + (tid >> 2), c = tid & 3;
+  if (gr < nrows) {
+    const bf16_t* src = base + (long)gr * stride + 8 * c;
+    r[0] = *(const uint4*)src;
+    r[1] = *(const uint4*)(src + 32);
+    rope_load8(rope, gr, 8 * c, cs);
+  } else {
+    r[0] = r[1] = make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) cs[e] = 0.f;
+  }
+}
+__device__ __forceinline__ void pair_store_k(char* t, const uint4 (&r)[2], int tid) {
+  const int row = tid >> 2, c = tid & 3;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) *(uint4*)(t + kmaj_off(row, c + 4 * i)) = r[i];
+}
+__device__ __forceinline__ void pair_store_mn(char* t, const uint4 (&r)[2], int tid, bool perm) {
+  const int row = perm ? rho(tid >> 2) : tid >> 2, c = tid & 3;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) *(uint4*)(t + mnmaj_off<64>(row, 2 * (c + 4 * i))) = r[i];
 }
 
 __device__ __forceinline__ s16x8_t pack_frag(const f32x4_t& a, const f32x4_t& b) {
@@ -136,7 +228,7 @@ __device__ __forceinline__ uint32_t attn_keep_bwd(int qb, int kvw, uint32_t bh, 
 }
 
 // ============================================================== forward
-template <bool DROP>
+template <bool DROP, bool ROPE>
 __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict__ Q,
                                                         const bf16_t* __restrict__ K,
                                                         const bf16_t* __restrict__ V,
@@ -145,7 +237,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
                                                         int Sk, long qs, long kvs, long os,
                                                         long qb, long kvb, long ob,
                                                         int causal, float scale,
-                                                        const int* __restrict__ kv_len, LnDrop drop) {
+                                                        const int* __restrict__ kv_len, LnDrop drop,
+                                                        const float* __restrict__ rope) {
   __shared__ __attribute__((aligned(16))) char smem[2 * AT * AD * 2];
   char* kt = smem;
   char* vt = smem + AT * AD * 2;
@@ -168,6 +261,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
     if (qw < Sq) qf[ks] = *(const s16x8_t*)(Qb + (long)qw * qs + 32 * ks + 8 * g);
     else qf[ks] = s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
   }
+  if (ROPE && qw < Sq) rope_rot_frag(qf, rope, qw, g);
   const float sl2 = scale * kLog2e;
   float m = -1e30f, l = 0.f;
   f32x4_t o[4];
@@ -178,18 +272,24 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const bf16_t* __restrict_
   if (causal) kend = min(kend, q0 + AT);
   // the next K / V tile is fetched into registers right after the current
   // one reaches LDS, so its global latency hides under this tile's math
+  // (ROPE: K by the pair mapping with its table rows, rotated when it lands)
   uint4 rk[2], rv[2];
+  float kcs[16];
   if (kend > 0) {
-    tile_fetch(Kb, kvs, 0, klen, rk, tid);
+    if (ROPE) pair_fetch(Kb, kvs, 0, klen, rope, rk, kcs, tid);
+    else tile_fetch(Kb, kvs, 0, klen, rk, tid);
     tile_fetch(Vb, kvs, 0, klen, rv, tid);
   }
   for (int k0 = 0; k0 < kend; k0 += AT) {
+    if (ROPE) rope_rot8(rk[0], rk[1], kcs);
     __syncthreads();   // previous tile fully consumed
-    tile_store_k(kt, rk, tid, false);
+    if (ROPE) pair_store_k(kt, rk, tid);
+    else tile_store_k(kt, rk, tid, false);
     tile_store_mn(vt, rv, tid, true);
     __syncthreads();
     if (k0 + AT < kend) {
-      tile_fetch(Kb, kvs, k0 + AT, klen, rk, tid);
+      if (ROPE) pair_fetch(Kb, kvs, k0 + AT, klen, rope, rk, kcs, tid);
+      else tile_fetch(Kb, kvs, k0 + AT, klen, rk, tid);
       tile_fetch(Vb, kvs, k0 + AT, klen, rv, tid);
     }
     // S^T[kv][q] : 4 kv sub-tiles x 2 k-steps
@@ -282,13 +382,13 @@ __global__ void attn_delta_kernel(const bf16_t* __restrict__ O, const bf16_t* __
 }
 
 // ============================================================== backward
-template <bool DROP>
+template <bool DROP, bool ROPE>
 __global__ void __launch_bounds__(256) attn_bwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ dO, const float* __restrict__ LSE, const float* __restrict__ DELTA,
     bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, float* __restrict__ dQacc, int H, int Sq,
     int Sk, long qs, long kvs, long os, long qb, long kvb, long ob, int causal, float scale,
-    const int* __restrict__ kv_len, LnDrop drop) {
+    const int* __restrict__ kv_len, LnDrop drop, const float* __restrict__ rope) {
   // LDS: Q row image, Q^T image (rho), dO row image, dO^T image (rho), K^T image, dS image,
   //      lse[64], delta[64]
   __shared__ __attribute__((aligned(16))) char smem[6 * AT * AD * 2 + 2 * AT * 4];
@@ -322,10 +422,18 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
     kf[ks] = ok ? *(const s16x8_t*)(Kb + (long)kvw * kvs + 32 * ks + 8 * g) : s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
     vf[ks] = ok ? *(const s16x8_t*)(Vb + (long)kvw * kvs + 32 * ks + 8 * g) : s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
   }
+  if (ROPE && kvw < klen) rope_rot_frag(kf, rope, kvw, g);
   {  // K image [kv][d] for dQ = dS K (B operand, k = kv, n = d: MN-major)
     uint4 rk[2];
-    tile_fetch(Kb, kvs, k0, klen, rk, tid);
-    tile_store_mn(k_mn, rk, tid, false);
+    if (ROPE) {
+      float cs[16];
+      pair_fetch(Kb, kvs, k0, klen, rope, rk, cs, tid);
+      rope_rot8(rk[0], rk[1], cs);
+      pair_store_mn(k_mn, rk, tid, false);
+    } else {
+      tile_fetch(Kb, kvs, k0, klen, rk, tid);
+      tile_store_mn(k_mn, rk, tid, false);
+    }
   }
   f32x4_t dvt[4], dkt[4];
 #pragma unroll
@@ -337,11 +445,19 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
   const int qstart = causal ? (k0 / AT) * AT : 0;
   for (int q0 = qstart; q0 < Sq; q0 += AT) {
     uint4 rq[2], rd[2];
-    tile_fetch(Qb, qs, q0, Sq, rq, tid);
+    float qcs[16];
+    if (ROPE) pair_fetch(Qb, qs, q0, Sq, rope, rq, qcs, tid);
+    else tile_fetch(Qb, qs, q0, Sq, rq, tid);
     tile_fetch(dOb, os, q0, Sq, rd, tid);
+    if (ROPE) rope_rot8(rq[0], rq[1], qcs);   // one rotated copy feeds both Q images
     __syncthreads();   // previous iteration done with all images
-    tile_store_k(q_k, rq, tid, false);
-    tile_store_mn(q_mn, rq, tid, true);
+    if (ROPE) {
+      pair_store_k(q_k, rq, tid);
+      pair_store_mn(q_mn, rq, tid, true);
+    } else {
+      tile_store_k(q_k, rq, tid, false);
+      tile_store_mn(q_mn, rq, tid, true);
+    }
     tile_store_k(do_k, rd, tid, false);
     tile_store_mn(do_mn, rd, tid, true);
     if (tid < AT) {
@@ -430,6 +546,10 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) dvt[mt] *= drop.scale;
     }
+    if (ROPE) {   // dk = R^T dk': dkt[mt] / dkt[mt + 2] hold d = 16 mt + 4g + r and d + 32
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) rope_inv4(dkt[mt], dkt[mt + 2], rope, kvw, 16 * mt + 4 * g);
+    }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
       const int d = 16 * mt + 4 * g;
@@ -450,13 +570,13 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(
 // dO and O tile images. One launch instead of delta+zero / backward /
 // fp32-dQ cast, and no dQ atomics.
 constexpr int ATS_K = 128;
-template <bool DROP>
+template <bool DROP, bool ROPE>
 __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
     const bf16_t* __restrict__ O, const bf16_t* __restrict__ dO, const float* __restrict__ LSE,
     bf16_t* __restrict__ dQ, bf16_t* __restrict__ dK, bf16_t* __restrict__ dV, int H, int Sq, int Sk,
     long qs, long kvs, long os, long qb, long kvb, long ob, int causal, float scale,
-    const int* __restrict__ kv_len, LnDrop drop) {
+    const int* __restrict__ kv_len, LnDrop drop, const float* __restrict__ rope) {
   // LDS: Q row image, Q^T image (rho), dO row image, dO^T image (rho), O row
   //      image (delta), K [kv][d] image (128 rows), dS [kv][q] image (128 rows),
   //      lse[64], delta[64]
@@ -488,11 +608,14 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
   // query tile q0's Q (half 0) / dO, O (half 1) rows and LSE, fetched into
   // registers one tile AHEAD: the first with the K / V loads below, the next
   // right after the current one reaches LDS (its latency hides under the math)
+  // (ROPE: Q by the pair mapping with its table rows, rotated when it lands)
   uint4 ra[2], rb[2];
+  float qcs[16];
   float lse_r = 0.f;
   auto fetch_q = [&](int q0) {
     if (half == 0) {
-      tile_fetch(Qb, qs, q0, Sq, ra, ht);
+      if (ROPE) pair_fetch(Qb, qs, q0, Sq, rope, ra, qcs, ht);
+      else tile_fetch(Qb, qs, q0, Sq, ra, ht);
       if (ht < AT) lse_r = q0 + ht < Sq ? lse_b[q0 + ht] : 0.f;
     } else {
       tile_fetch(dOb, os, q0, Sq, ra, ht);
@@ -507,13 +630,21 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
     kf[ks] = ok ? *(const s16x8_t*)(Kb + (long)kvw * kvs + 32 * ks + 8 * g) : s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
     vf[ks] = ok ? *(const s16x8_t*)(Vb + (long)kvw * kvs + 32 * ks + 8 * g) : s16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
   }
+  if (ROPE && kvw < klen) rope_rot_frag(kf, rope, kvw, g);
   {  // K image: half 0 keys 0-63, half 1 keys 64-127 (rows 64*half + r)
     uint4 rk[2];
-    tile_fetch(Kb, kvs, 64 * half, klen, rk, ht);
+    if (ROPE) {
+      float cs[16];
+      pair_fetch(Kb, kvs, 64 * half, klen, rope, rk, cs, ht);
+      rope_rot8(rk[0], rk[1], cs);
+      pair_store_mn(k_mn + half * T, rk, ht, false);   // (the swizzle has period 16 rows)
+    } else {
+      tile_fetch(Kb, kvs, 64 * half, klen, rk, ht);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int row = 64 * half + (ht >> 3) + 32 * i;
-      *(uint4*)(k_mn + mnmaj_off<64>(row, 2 * (ht & 7))) = rk[i];
+      for (int i = 0; i < 2; ++i) {
+        const int row = 64 * half + (ht >> 3) + 32 * i;
+        *(uint4*)(k_mn + mnmaj_off<64>(row, 2 * (ht & 7))) = rk[i];
+      }
     }
   }
   f32x4_t dvt[4], dkt[4];
@@ -525,10 +656,16 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
 
   for (int q0 = 0; q0 < Sq; q0 += AT) {
     // half 0 stages Q, half 1 stages dO and O (fetched one tile ahead)
+    if (ROPE && half == 0) rope_rot8(ra[0], ra[1], qcs);   // one rotated copy feeds both Q images
     __syncthreads();   // previous iteration done with all images
     if (half == 0) {
-      tile_store_k(q_k, ra, ht, false);
-      tile_store_mn(q_mn, ra, ht, true);
+      if (ROPE) {
+        pair_store_k(q_k, ra, ht);
+        pair_store_mn(q_mn, ra, ht, true);
+      } else {
+        tile_store_k(q_k, ra, ht, false);
+        tile_store_mn(q_mn, ra, ht, true);
+      }
       if (ht < AT) s_lse[ht] = lse_r * kLog2e;
     } else {
       tile_store_k(do_k, ra, ht, false);
@@ -603,14 +740,36 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
     }
     __syncthreads();
     // dQ[q][d] over all 128 keys: wave w -> q rows 16*(w&3), d columns 32*(w>>2) + {0, 16}
+    // (ROPE: columns 16*(w>>2) + {0, 32}, so dq[0][r] / dq[1][r] are a pair)
+    constexpr int DW = ROPE ? 16 : 32, DN = ROPE ? 32 : 16;
     f32x4_t dq[2];
     dq[0] = dq[1] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    // (ROPE: rows q of the table at frequency j = this lane's column, loaded
+    // ahead of the MFMAs that hide them)
+    float dqc[4], dqs[4];
+    if (ROPE) {
+      const int j = DW * (w >> 2) + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = q0 + 16 * (w & 3) + 4 * g + r;
+        dqc[r] = q < Sq ? rope[(long)q * 64 + j] : 0.f;
+        dqs[r] = q < Sq ? rope[(long)q * 64 + 32 + j] : 0.f;
+      }
+    }
 #pragma unroll
     for (int s = 0; s < ATS_K / 32; ++s) {
       const s16x8_t a = read_frag_mn<64>(ds_mn, lane, 32 * s, 16 * (w & 3));
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
-        dq[nt] = mfma(a, read_frag_mn<64>(k_mn, lane, 32 * s, 32 * (w >> 2) + 16 * nt), dq[nt]);
+        dq[nt] = mfma(a, read_frag_mn<64>(k_mn, lane, 32 * s, DW * (w >> 2) + DN * nt), dq[nt]);
+    }
+    if (ROPE) {   // dq = R^T dq'
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float x = dq[0][r], y = dq[1][r];
+        dq[0][r] = x * dqc[r] + y * dqs[r];
+        dq[1][r] = y * dqc[r] - x * dqs[r];
+      }
     }
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
@@ -618,7 +777,7 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
       for (int r = 0; r < 4; ++r) {
         const int q = q0 + 16 * (w & 3) + 4 * g + r;
         if (q < Sq) {
-          const int d = 32 * (w >> 2) + 16 * nt + (lane & 15);
+          const int d = DW * (w >> 2) + DN * nt + (lane & 15);
           dQ[(long)b * qb + (long)q * qs + h * AD + d] = f2bf(dq[nt][r] * scale);
         }
       }
@@ -629,6 +788,10 @@ __global__ void __launch_bounds__(512) attn_bwd_short_kernel(
     if (DROP) {
 #pragma unroll
       for (int mt = 0; mt < 4; ++mt) dvt[mt] *= drop.scale;
+    }
+    if (ROPE) {   // dk = R^T dk': dkt[mt] / dkt[mt + 2] hold d = 16 mt + 4g + r and d + 32
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) rope_inv4(dkt[mt], dkt[mt + 2], rope, kvw, 16 * mt + 4 * g);
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) {
@@ -650,16 +813,45 @@ __global__ void attn_dq_cast_kernel(const float* __restrict__ acc, bf16_t* __res
   }
 }
 
+// ROPE: the same from the fp32 accumulator of dq' -- a thread reads d = j and
+// j + 32 of a (token, head) row, applies the transposed rotation and stores both
+__global__ void attn_dq_cast_rope_kernel(const float* __restrict__ acc, bf16_t* __restrict__ dq, long npair,
+                                         int H, int Sq, long qs, long qb, const float* __restrict__ rope) {
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < npair; i += (long)gridDim.x * blockDim.x) {
+    const int j = (int)(i & 31);
+    const long th = i >> 5;              // token * H + head
+    const long tok = th / H;
+    const int h = (int)(th % H), q = (int)(tok % Sq);
+    const float x = acc[th * AD + j], y = acc[th * AD + 32 + j];
+    const float c = rope[(long)q * 64 + j], sn = rope[(long)q * 64 + 32 + j];
+    bf16_t* out = dq + (tok / Sq) * qb + (long)q * qs + h * AD + j;
+    out[0] = f2bf(x * c + y * sn);
+    out[32] = f2bf(y * c - x * sn);
+  }
+}
+
+// the four (DROP, ROPE) instantiations of a kernel by the two optional arguments
+#define TAM_ATTN_PICK(LAUNCH)                   \
+  do {                                          \
+    if (rope) {                                 \
+      if (drop.rec) LAUNCH(true, true);         \
+      else LAUNCH(false, true);                 \
+    } else {                                    \
+      if (drop.rec) LAUNCH(true, false);        \
+      else LAUNCH(false, false);                \
+    }                                           \
+  } while (0)
+
 void attn_forward(const bf16_t* q, const bf16_t* k, const bf16_t* v, bf16_t* o, float* lse, int B,
                   int H, int Sq, int Sk, long q_stride, long kv_stride, long o_stride, long q_bstride,
                   long kv_bstride, long o_bstride, int causal, float scale, const int* kv_len, hipStream_t s,
-                  LnDrop drop) {
+                  LnDrop drop, const float* rope) {
   dim3 grid((Sq + AT - 1) / AT, B * H);
-#define TAM_ATTN_FWD(DR)                                                                                  \
-  hipLaunchKernelGGL(attn_fwd_kernel<DR>, grid, dim3(256), 0, s, q, k, v, o, lse, H, Sq, Sk, q_stride,   \
-                     kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal, scale, kv_len, drop)
-  if (drop.rec) TAM_ATTN_FWD(true);
-  else TAM_ATTN_FWD(false);
+#define TAM_ATTN_FWD(DR, RP)                                                                               \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_fwd_kernel<DR, RP>), grid, dim3(256), 0, s, q, k, v, o, lse, H,  \
+                     Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal,      \
+                     scale, kv_len, drop, rope)
+  TAM_ATTN_PICK(TAM_ATTN_FWD);
 #undef TAM_ATTN_FWD
 }
 
@@ -673,14 +865,13 @@ void attn_backward(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16
                    const bf16_t* dout, const float* lse, bf16_t* dq, bf16_t* dk, bf16_t* dv,
                    float* dq_acc, float* delta, int B, int H, int Sq, int Sk, long q_stride,
                    long kv_stride, long o_stride, long q_bstride, long kv_bstride, long o_bstride, int causal,
-                   float scale, const int* kv_len, hipStream_t s, LnDrop drop) {
+                   float scale, const int* kv_len, hipStream_t s, LnDrop drop, const float* rope) {
   if (Sk <= ATS_K && g_attn_short) {
-#define TAM_ATTN_BWD_SHORT(DR)                                                                                 \
-  hipLaunchKernelGGL(attn_bwd_short_kernel<DR>, dim3(B * H), dim3(512), 0, s, q, k, v, o, dout, lse, dq, dk,  \
-                     dv, H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal,  \
-                     scale, kv_len, drop)
-    if (drop.rec) TAM_ATTN_BWD_SHORT(true);
-    else TAM_ATTN_BWD_SHORT(false);
+#define TAM_ATTN_BWD_SHORT(DR, RP)                                                                          \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_bwd_short_kernel<DR, RP>), dim3(B * H), dim3(512), 0, s, q, k, v, \
+                     o, dout, lse, dq, dk, dv, H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride,         \
+                     kv_bstride, o_bstride, causal, scale, kv_len, drop, rope)
+    TAM_ATTN_PICK(TAM_ATTN_BWD_SHORT);
 #undef TAM_ATTN_BWD_SHORT
     return;
   }
@@ -689,17 +880,21 @@ void attn_backward(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16
                      B, H, Sq, o_stride, o_bstride);
   const long nq = (long)B * Sq * H * AD;
   dim3 grid((Sk + AT - 1) / AT, B * H);
-#define TAM_ATTN_BWD(DR)                                                                                  \
-  hipLaunchKernelGGL(attn_bwd_kernel<DR>, grid, dim3(256), 0, s, q, k, v, dout, lse, delta, dk, dv, dq_acc, \
-                     H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride, kv_bstride, o_bstride, causal,  \
-                     scale, kv_len, drop)
-  if (drop.rec) TAM_ATTN_BWD(true);
-  else TAM_ATTN_BWD(false);
+#define TAM_ATTN_BWD(DR, RP)                                                                               \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(attn_bwd_kernel<DR, RP>), grid, dim3(256), 0, s, q, k, v, dout, lse,  \
+                     delta, dk, dv, dq_acc, H, Sq, Sk, q_stride, kv_stride, o_stride, q_bstride,           \
+                     kv_bstride, o_bstride, causal, scale, kv_len, drop, rope)
+  TAM_ATTN_PICK(TAM_ATTN_BWD);
 #undef TAM_ATTN_BWD
-  long blocks = (nq + 255) / 256;
+  long blocks = ((rope ? nq / 2 : nq) + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(attn_dq_cast_kernel, dim3(blocks), dim3(256), 0, s, dq_acc, dq, nq, H * AD, Sq,
-                     q_stride, q_bstride);
+  if (rope)
+    hipLaunchKernelGGL(attn_dq_cast_rope_kernel, dim3(blocks), dim3(256), 0, s, dq_acc, dq, nq / 2, H, Sq,
+                       q_stride, q_bstride, rope);
+  else
+    hipLaunchKernelGGL(attn_dq_cast_kernel, dim3(blocks), dim3(256), 0, s, dq_acc, dq, nq, H * AD, Sq,
+                       q_stride, q_bstride);
 }
+#undef TAM_ATTN_PICK
 
 }  // namespace tam

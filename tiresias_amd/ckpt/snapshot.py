@@ -80,7 +80,11 @@ class SnapshotWriter:
         else:
             host = {k: v.detach().clone() for k, v in state.items()}
             ev = None
-        self._q.put((jid, step, host, ev))
+        # a rotary-position job's arena has the sizes of a sinusoid job's: the
+        # file names the encoding, so load_snapshot can refuse the other kind
+        # (a job that did not ask: the file as it always was)
+        extra = {"pos": "rope"} if getattr(trainer, "pos", None) == "rope" else {}
+        self._q.put((jid, step, host, ev, extra))
 
     def _loop(self) -> None:
         while True:
@@ -90,7 +94,7 @@ class SnapshotWriter:
             if isinstance(item, threading.Event):
                 item.set()
                 continue
-            jid, step, host, ev = item
+            jid, step, host, ev, extra = item
             try:
                 if ev is not None:
                     ev.synchronize()
@@ -99,7 +103,7 @@ class SnapshotWriter:
                         continue
                 path = self.path_of(jid)
                 tmp = path + ".tmp"
-                torch.save({"job": jid, "step": step, "state": host}, tmp)
+                torch.save({"job": jid, "step": step, "state": host, **extra}, tmp)
                 os.replace(tmp, path)
                 nb = sum(t.numel() * t.element_size() for t in host.values())
                 with self._lock:
@@ -155,6 +159,12 @@ def load_snapshot(path: str, trainer) -> int:
     framework wrote are loaded, and with ``weights_only=True``."""
     d = torch.load(path, map_location="cpu", weights_only=True)
     st = trainer.state_tensors()
+    # the position encoding moves no buffer, so it is an explicit field: a
+    # model trained with one encoding is not continued with the other
+    have_pos, want_pos = d.get("pos", "sinusoid"), getattr(trainer, "pos", "sinusoid")
+    if have_pos != want_pos:
+        raise ValueError(f"snapshot {path}: it was written by a pos={have_pos} job, the trainer is pos={want_pos} "
+                         "(a snapshot restores only into a trainer of the same position encoding)")
     # a BatchNorm model's snapshot carries running statistics, a GroupNorm
     # model's none: the other kind is refused before anything is written
     have = {k for k in d["state"] if k.startswith("buf.")}

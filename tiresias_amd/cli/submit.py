@@ -12,6 +12,7 @@ Examples::
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --batch 4 --iterations 800 --norm group
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --iterations 800 --cardinality 32
     python -m tiresias_amd.cli.submit --spool /tmp/tam --model resnet50 --iterations 800 --se-ratio 16
+    python -m tiresias_amd.cli.submit --spool /tmp/tam --model transformer --iterations 800 --pos rope
     python -m tiresias_amd.cli.submit --spool /tmp/tam --status
     python -m tiresias_amd.cli.submit --spool /tmp/tam --shutdown
 """
@@ -62,6 +63,10 @@ def main(argv=None) -> int:
                          "(sample, channel) through two FCs C -> max(8, C / R) -> C (R in 4, 8, 16, 32; resnet50 "
                          "with 16 is SE-ResNet-50, with --cardinality 32 SE-ResNeXt-50 32x4d); other models "
                          "reject it")
+    ap.add_argument("--pos", choices=("sinusoid", "rope"),
+                    help="position encoding of a Transformer job: rope rotates Q and K inside the self-attention "
+                         "kernels (rotary embeddings, pairs (j, j + 32), base 10000) in place of the additive "
+                         "sinusoid table; other models reject it; default sinusoid")
     ap.add_argument("--status", action="store_true")
     ap.add_argument("--shutdown", action="store_true", help="stop serving once the cluster drains")
     a = ap.parse_args(argv)
@@ -78,7 +83,7 @@ def main(argv=None) -> int:
     jid = sp.submit(a.model, a.gpus, iterations=a.iterations, duration=a.duration, job_id=a.job_id,
                     batch=a.batch, grad_clip=a.grad_clip, dropout=a.dropout,
                     attn_dropout=a.attn_dropout, opt_dtype=a.opt_dtype, trust_ratio=a.trust_ratio,
-                    norm=a.norm, cardinality=a.cardinality, se_ratio=a.se_ratio)
+                    norm=a.norm, cardinality=a.cardinality, se_ratio=a.se_ratio, pos=a.pos)
     print(jid)
     return 0
 

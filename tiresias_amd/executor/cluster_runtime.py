@@ -154,6 +154,7 @@ class ReplayJob:
     norm: Optional[str] = None           # normalisation of a CNN job: "batch" / "group" (None = batch)
     cardinality: Optional[int] = None    # ResNeXt cardinality of a ResNet job (None = the plain model)
     se_ratio: Optional[int] = None       # Squeeze-and-Excitation ratio of a ResNet job (None = no SE blocks)
+    pos: Optional[str] = None            # position encoding of a Transformer job: "sinusoid" / "rope" (None = sinusoid)
 
 
 class Controller:
@@ -519,6 +520,7 @@ class Controller:
                 norm = self._validate_norm(req, model)
                 card = self._validate_cardinality(req, model)
                 se = self._validate_se_ratio(req, model)
+                pos = self._validate_pos(req, model)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -532,7 +534,7 @@ class Controller:
                            num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
             self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
                                         dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta,
-                                        norm=norm, cardinality=card, se_ratio=se)
+                                        norm=norm, cardinality=card, se_ratio=se, pos=pos)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -645,6 +647,18 @@ class Controller:
 
         return check_se_ratio(model, req.get("se_ratio"))
 
+    @staticmethod
+    def _validate_pos(req: dict, model: str) -> Optional[str]:
+        """The request's ``pos`` key (absent / null: None, the model's own
+        position encoding); ValueError for a value that is not one or a model
+        without self-attention."""
+        from .trainer import check_pos
+
+        pos = req.get("pos")
+        if pos is not None:
+            check_pos(model, pos)
+        return pos
+
     def status(self) -> dict:
         s = self.sched
         jobs = {}
@@ -713,6 +727,8 @@ class Controller:
                     act["cardinality"] = rj.cardinality
                 if rj.se_ratio is not None:
                     act["se_ratio"] = rj.se_ratio
+                if rj.pos is not None:
+                    act["pos"] = rj.pos
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
                     act["source"] = "snapshot"
@@ -956,7 +972,9 @@ class Worker:
         the per-job setters (clip, dropouts, trust ratio) are not part of the key.
         A GroupNorm job's model has other layers and no running statistics, so
         its key carries ``norm`` too, a ResNeXt job's its ``cardinality`` and an
-        SE job's its ``se_ratio``."""
+        SE job's its ``se_ratio``. A rotary-position job has the same buffers
+        but another forward (and another captured graph): its key carries
+        ``pos``."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
         if act.get("opt_dtype") in ("bf16", "factored"):
             key += (act["opt_dtype"],)
@@ -964,7 +982,9 @@ class Worker:
             key += ("norm=group",)
         if act.get("cardinality") is not None:
             key += (f"cardinality={act['cardinality']}",)
-        return key + (f"se_ratio={act['se_ratio']}",) if act.get("se_ratio") is not None else key
+        if act.get("se_ratio") is not None:
+            key += (f"se_ratio={act['se_ratio']}",)
+        return key + ("pos=rope",) if act.get("pos") == "rope" else key
 
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
@@ -995,6 +1015,9 @@ class Worker:
             if free[-1].se_ratio != act.get("se_ratio"):
                 raise RuntimeError(f"warm pool {key}: a se_ratio={free[-1].se_ratio} trainer is pooled under "
                                    f"the key of a se_ratio={act.get('se_ratio')} job")
+            if free[-1].pos != (act.get("pos") or "sinusoid"):
+                raise RuntimeError(f"warm pool {key}: a pos={free[-1].pos} trainer is pooled under the key of a "
+                                   f"pos={act.get('pos') or 'sinusoid'} job")
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
             t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
@@ -1010,7 +1033,7 @@ class Worker:
                     ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
                     attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"),
                     trust_ratio=act.get("trust_ratio"), norm=act.get("norm"),
-                    cardinality=act.get("cardinality"), se_ratio=act.get("se_ratio"))
+                    cardinality=act.get("cardinality"), se_ratio=act.get("se_ratio"), pos=act.get("pos"))
         t.pool_key = key
         return t
 
@@ -1351,7 +1374,8 @@ class Worker:
                     t.rebind(self._group(ranks))
                     # (the trainer's own state format, whatever the action carries)
                     t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype, norm=t.norm,
-                                                        cardinality=t.cardinality, se_ratio=t.se_ratio))
+                                                        cardinality=t.cardinality, se_ratio=t.se_ratio,
+                                                        pos=t.pos))
                 elif self.rank in ranks:
                     self._bind(self.trainers[a["job"]], ranks)
                 if self.rank in ranks and "step" in a:

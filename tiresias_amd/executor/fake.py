@@ -88,6 +88,7 @@ class FakeCluster:
         self.norm: Dict[str, Optional[str]] = {}     # job -> normalisation it was started with (start action's norm)
         self.card: Dict[str, Optional[int]] = {}     # job -> ResNeXt cardinality it was started with
         self.se: Dict[str, Optional[int]] = {}       # job -> Squeeze-and-Excitation ratio it was started with
+        self.pos: Dict[str, Optional[str]] = {}      # job -> position encoding it was started with
         self.groups: Set[Tuple[int, ...]] = set()
         self.stats = {"p2p_bytes": 0.0, "spill_bytes": 0.0, "restore_bytes": 0.0, "starts": 0,
                       "resident_resumes": 0, "rounds": 0}
@@ -202,6 +203,14 @@ class FakeCluster:
                     raise ProtocolError(f"start of {job} with se_ratio {se!r}, its state was built with "
                                         f"{self.se.get(job)!r}")
                 self.se[job] = se
+                # pos fixes a job's forward: no state, no cost to the world
+                # model, but every start of a job carries the same one
+                if a.get("pos") not in (None, "sinusoid", "rope"):
+                    raise ProtocolError(f"start of {job} with pos {a.get('pos')!r}")
+                if job in self.held and self.pos.get(job) != a.get("pos"):
+                    raise ProtocolError(f"start of {job} with pos {a.get('pos')!r}, its state was built with "
+                                        f"{self.pos.get(job)!r}")
+                self.pos[job] = a.get("pos")
                 src = a["source"]
                 b = _state_bytes(a["model"], a.get("opt_dtype"))
                 if src == "fresh":

@@ -24,7 +24,9 @@ Request schema (JSON)::
 A job that asks for ``--norm`` carries one more key, ``"norm": "batch" |
 "group"`` (ResNet models); a request without it is written as before. The
 same holds for ``--cardinality``: ``"cardinality": G`` (ResNeXt, ResNet models)
-and for ``--se-ratio``: ``"se_ratio": R`` (Squeeze-and-Excitation, ResNet models).
+and for ``--se-ratio``: ``"se_ratio": R`` (Squeeze-and-Excitation, ResNet models)
+and for ``--pos``: ``"pos": "sinusoid" | "rope"`` (position encoding, Transformer
+models).
 """
 from __future__ import annotations
 
@@ -55,7 +57,7 @@ class Spool:
                dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
                opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
                norm: Optional[str] = None, cardinality: Optional[int] = None,
-               se_ratio: Optional[int] = None) -> str:
+               se_ratio: Optional[int] = None, pos: Optional[str] = None) -> str:
         if iterations is None and duration is None:
             raise ValueError("give iterations or duration")
         jid = job_id or f"sub-{time.time_ns()}-{os.getpid()}"
@@ -69,6 +71,8 @@ class Spool:
             req["cardinality"] = cardinality
         if se_ratio is not None:
             req["se_ratio"] = se_ratio
+        if pos is not None:
+            req["pos"] = pos
         _atomic_write(os.path.join(self.root, "incoming", f"{jid}.json"), req)
         return jid
 

@@ -31,7 +31,7 @@ class Trainer:
                  dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
                  opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
                  norm: Optional[str] = None, cardinality: Optional[int] = None,
-                 se_ratio: Optional[int] = None):
+                 se_ratio: Optional[int] = None, pos: Optional[str] = None):
         self.model_name = model
         self.spec = MODELS[model]
         # normalisation of a CNN job (README "GroupNorm"): "group" builds the
@@ -48,6 +48,11 @@ class Trainer:
         # adds an SE block (four parameters, the se.hip kernels) to every
         # bottleneck. Structure again: construction, pool key, no setter
         self.se_ratio = check_se_ratio(model, self.spec.se_ratio if se_ratio is None else se_ratio)
+        # position encoding of a Transformer job (README "rotary position embeddings"):
+        # "rope" rotates Q and K inside the self-attention kernels in place of
+        # the additive table. No parameter moves, but the model's forward is
+        # another one: construction, pool key, no setter
+        self.pos = check_pos(model, self.spec.pos if pos is None else pos)
         if opt_dtype is None:
             opt_dtype = self.spec.opt_dtype
         if opt_dtype not in (None, "fp32", "bf16", "factored"):
@@ -99,6 +104,8 @@ class Trainer:
             mk["cardinality"] = self.cardinality
         if self.se_ratio is not None:
             mk["se_ratio"] = self.se_ratio
+        if self.pos == "rope":
+            mk["pos"] = "rope"
         self.model = make_model(model, self.arena, **mk)
         self.arena.materialize()
         n = self.arena.numel
@@ -1001,6 +1008,20 @@ def check_se_ratio(model: str, v) -> Optional[int]:
     if not getattr(MODELS[model].builder, "se_ratios", False):
         raise ValueError(f"se_ratio={v!r}: {model!r} has no bottleneck to put an SE block on (the knob is for the "
                          "ResNet models)")
+    return v
+
+
+def check_pos(model: str, v) -> str:
+    """The position encoding a job of ``model`` runs with ("sinusoid" when
+    ``v`` is None); ValueError for a value that is not one, or for a model
+    whose builder has no self-attention to rotate in."""
+    if v is None:
+        return "sinusoid"
+    if not isinstance(v, str) or v not in ("sinusoid", "rope"):
+        raise ValueError(f"pos must be 'sinusoid' or 'rope', got {v!r}")
+    if v not in getattr(MODELS[model].builder, "positions", ()):
+        raise ValueError(f"pos={v!r}: {model!r} has no position encoding to choose (the knob is for the "
+                         "Transformer models)")
     return v
 
 

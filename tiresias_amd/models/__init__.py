@@ -72,6 +72,11 @@ class ModelSpec:
     # --se-ratio): None keeps the plain bottleneck, r in {4, 8, 16, 32} adds an
     # SE block to each (ResNet models; others reject it). No shipped model sets it
     se_ratio: Optional[int] = None
+    # position encoding of a Transformer job (Trainer pos, --pos): None /
+    # "sinusoid" keep the additive table of the embedding kernel, "rope" rotates
+    # Q and K inside the self-attention kernels instead (the Transformer
+    # models; others reject it). No shipped model sets it
+    pos: Optional[str] = None
 
 
 MODELS: Dict[str, ModelSpec] = {

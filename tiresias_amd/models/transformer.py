@@ -23,6 +23,12 @@ drops softmax probabilities inside the attention kernels of the encoder
 self-attention, the decoder self-attention and the decoder cross-attention;
 p is quantised to 1/256 and the mask is regenerated in the attention backward
 (ops/functional.py "dropout", csrc/include/tam/philox.h).
+Position (``pos="sinusoid"``, the default: the paper's table, added in the
+embedding kernel; ``pos="rope"``: rotary embeddings, Su et al. 2021): with
+``rope`` the embeddings add no table and the encoder and decoder
+self-attention rotate Q and K inside the attention kernels, forward and
+backward, from a constant cos / sin table (``Fx.rope_table``); cross-attention
+stays unrotated. Parameters, names and arena order are the same either way.
 """
 from __future__ import annotations
 
@@ -36,15 +42,22 @@ from ..ops.arena import Arena
 
 class TransformerBase:
     name = "transformer"
+    positions = ("sinusoid", "rope")     # what Trainer(pos=) / submit --pos may ask of this model
 
     def __init__(self, arena: Arena, vocab: int = 32000, d: int = 512, heads: int = 8,
                  ffn: int = 2048, enc_layers: int = 6, dec_layers: int = 6, max_len: int = 1024,
-                 dropout: float = 0.0, attn_dropout: float = 0.0):
+                 dropout: float = 0.0, attn_dropout: float = 0.0, pos: str = "sinusoid"):
         assert d == heads * 64, "kernels are built for head_dim 64"
+        if pos not in self.positions:
+            raise ValueError(f"pos must be 'sinusoid' or 'rope', got {pos!r}")
         A = arena
         self.arena, self.d, self.h, self.vocab = arena, d, heads, vocab
         self.emb = A.add("emb", (vocab, d), init="normal", std=d ** -0.5)
-        self.pos = self._sinusoid(max_len, d, arena.device)
+        # the position encoding's constant table: the additive sinusoid of the
+        # embedding kernel, or the cos / sin rows the self-attention kernels rotate by
+        self.pos_kind = pos
+        self.pos = self._sinusoid(max_len, d, arena.device) if pos == "sinusoid" else None
+        self.rope = Fx.rope_table(max_len, arena.device) if pos == "rope" else None
 
         def ln(n):
             return (A.add(n + ".g", (d,), init="ones", decay=False, fp32_compute=True),
@@ -91,6 +104,12 @@ class TransformerBase:
         on = self.training and self.attn_dropout and self.attn_dropout > 0
         return {"drop": self.attn_dropout} if on else {}
 
+    @property
+    def _rp(self):
+        """Keyword arguments of a self-attention call: the rotary table of a
+        ``pos="rope"`` model, nothing otherwise (the call as it was)."""
+        return {} if self.rope is None else {"rope": self.rope}
+
     @staticmethod
     def _sinusoid(n, d, dev):
         pos = torch.arange(n, dtype=torch.float32)[:, None]
@@ -102,9 +121,10 @@ class TransformerBase:
         return pe.to(device=dev, dtype=torch.bfloat16)
 
     def _embed(self, ids):
-        # scale + positional table in the embedding kernel (no broadcast copy)
-        return Fx.dropout(Fx.embedding(ids, self.emb, scale=math.sqrt(self.d), pos=self.pos[:ids.shape[1]]),
-                          self._p)
+        # scale + positional table in the embedding kernel (no broadcast copy);
+        # a rope model adds none (its positions enter in self-attention)
+        pos = None if self.pos is None else self.pos[:ids.shape[1]]
+        return Fx.dropout(Fx.embedding(ids, self.emb, scale=math.sqrt(self.d), pos=pos), self._p)
 
     def _ln_skip(self, x, r, p):
         """(x + r, LN(x + r)) with the residual add (and the dropout of r)
@@ -129,7 +149,7 @@ class TransformerBase:
         for L in self.enc:
             x, h = self._ln_skip(x, r, L["ln1"])
             qkv = Fx.linear(h, *L["qkv"])
-            a = Fx.self_attention(qkv, self.h, causal=False, **self._pa)
+            a = Fx.self_attention(qkv, self.h, causal=False, **self._pa, **self._rp)
             r = Fx.linear(a, *L["o"])
             x, r = self._ffn(x, r, L)
         return self._ln_skip(x, r, self.enc_ln)[1]
@@ -141,7 +161,7 @@ class TransformerBase:
         hold = {"n": 0}
         for i, L in enumerate(self.dec):
             x, h = self._ln_skip(x, r, L["ln1"])
-            a = Fx.self_attention(Fx.linear(h, *L["qkv"]), self.h, causal=True, **self._pa)
+            a = Fx.self_attention(Fx.linear(h, *L["qkv"]), self.h, causal=True, **self._pa, **self._rp)
             x, h = self._ln_skip(x, Fx.linear(a, *L["o"]), L["ln2"])
             q = Fx.linear(h, *L["q"])
             a = Fx.cross_attention(q, kv_all, self.h, k_slot=2 * i, v_slot=2 * i + 1, nkv=2 * n,

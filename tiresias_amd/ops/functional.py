@@ -1624,9 +1624,34 @@ def embedding(ids: torch.Tensor, table: Param, scale: float = 1.0, time_major: b
 
 
 # ============================================================ attention
-def _attn_ref(q, k, v, causal, scale, kv_len, drop=None):
+def rope_table(n: int, device) -> torch.Tensor:
+    """The rotary table of the attention kernels' ``rope`` argument: fp32
+    [n, 2, 32], row p = cos(p * w_j), then sin(p * w_j), w_j = 10000^(-j/32)
+    for the 32 pairs (j, j + 32) of a 64-wide head. Computed in fp64 and
+    rounded once; a constant (the kernels do no trigonometry)."""
+    w = torch.pow(torch.tensor(10000.0, dtype=torch.float64), -torch.arange(32, dtype=torch.float64) / 32)
+    ang = torch.arange(n, dtype=torch.float64)[:, None] * w[None, :]
+    return torch.stack([torch.cos(ang), torch.sin(ang)], 1).to(device=device, dtype=torch.float32).contiguous()
+
+
+def _rope_rotate(x, table):
+    # x [B,S,H,64] -> the kernels' MFMA operand: rotated in fp32 by the table's
+    # rows 0..S-1, rounded to bf16 once
+    S = x.shape[1]
+    c, s = table[:S, 0].float()[None, :, None, :], table[:S, 1].float()[None, :, None, :]
+    a, b = x.float()[..., :32], x.float()[..., 32:]
+    y = torch.cat([a * c - b * s, b * c + a * s], -1)
+    # (the rounding as a detached offset: under autograd the gradient passes it
+    # in fp32, as the kernels' dq = R^T dq' does before their one bf16 store)
+    return y + (y.to(BF16).float() - y).detach()
+
+
+def _attn_ref(q, k, v, causal, scale, kv_len, drop=None, rope=None):
     # q [B,Sq,H,64], k/v [B,Sk,H,64] -> o [B,Sq,H,64], lse [B,H,Sq]
     # drop = (record, site, thr, scale): the kernels' probability mask
+    # rope = the rotary table: q and k rotated (and rounded) as the kernels do
+    if rope is not None:
+        q, k = _rope_rotate(q, rope), _rope_rotate(k, rope)
     qf, kf, vf = (t.float().permute(0, 2, 1, 3) for t in (q, k, v))
     s = qf @ kf.transpose(-1, -2) * scale
     Sq, Sk = s.shape[-2], s.shape[-1]
@@ -1655,17 +1680,21 @@ class _Attn(Function):
     packed qkv tensor for both, slots 0/1/2). Gradients come back packed.
     drop = (record, site, thr, scale) from _attn_drop_args: dropout on the
     softmax probabilities inside the kernels, O = (keep * P) V * scale; the
-    backward regenerates the mask from the same tuple."""
+    backward regenerates the mask from the same tuple. rope: the rotary table
+    (``rope_table``); q and k are rotated inside the kernels and the gradients
+    come back with respect to the unrotated q and k."""
 
     @staticmethod
     def forward(ctx, q_src, kv_src, H: int, q_slot: int, nq: int, k_slot: int, v_slot: int,
-                nkv: int, causal: bool, kv_len, kv_hold=None, tm: bool = False, drop=None):
+                nkv: int, causal: bool, kv_len, kv_hold=None, tm: bool = False, drop=None, rope=None):
         # tm: q_src / kv_src / the output are time-major [S,B,.] (GNMT's
         # recurrent layout); the kernels take batch and token strides, so the
         # [B,S,H,64] views are transposes and no layout copy is made
         same = q_src is kv_src
         ctx.tm = tm
         ctx.drop = drop
+        # (no table: the op calls as they were)
+        ctx.rope = {} if rope is None else {"rope": rope}
         # kv_hold: several attention calls read different slots of ONE packed
         # K/V tensor (the decoder's batched cross-attention projection); they
         # write their slots into one shared gradient buffer and only the call
@@ -1683,9 +1712,9 @@ class _Attn(Function):
             ob = torch.empty((Sq, B, H, 64) if tm else (B, Sq, H, 64), dtype=BF16, device=q_src.device)
             o = ob.transpose(0, 1) if tm else ob
             lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q_src.device)
-            _T().attn_forward(qv, kv_, vv, o, lse, causal, scale, kv_len, *(drop or ()))
+            _T().attn_forward(qv, kv_, vv, o, lse, causal, scale, kv_len, *(drop or ()), **ctx.rope)
         else:
-            of, lse = _attn_ref(qv, kv_, vv, causal, scale, kv_len, drop)
+            of, lse = _attn_ref(qv, kv_, vv, causal, scale, kv_len, drop, rope)
             ob = (of.transpose(0, 1) if tm else of).to(BF16).contiguous()
         ctx.cfg = (same, H, q_slot, nq, k_slot, v_slot, nkv, causal, scale)
         ctx.save_for_backward(q_src, kv_src, ob, lse, kv_len)
@@ -1718,22 +1747,22 @@ class _Attn(Function):
             delta = torch.empty(B, H, Sq, dtype=torch.float32, device=q_src.device)
             _T().attn_backward(qv, kvv[:, :, k_slot], kvv[:, :, v_slot], o, do, lse, dqv,
                                dkvv[:, :, k_slot], dkvv[:, :, v_slot], dq_acc, delta, causal, scale,
-                               kv_len, *(ctx.drop or ()))
+                               kv_len, *(ctx.drop or ()), **ctx.rope)
         else:
             qf = qv.float().requires_grad_(True)
             kf = kvv[:, :, k_slot].float().requires_grad_(True)
             vf = kvv[:, :, v_slot].float().requires_grad_(True)
             with torch.enable_grad():
-                of, _ = _attn_ref(qf, kf, vf, causal, scale, kv_len, ctx.drop)
+                of, _ = _attn_ref(qf, kf, vf, causal, scale, kv_len, ctx.drop, ctx.rope.get("rope"))
                 gq, gk, gv = torch.autograd.grad(of, [qf, kf, vf], do.float())
             dqv.copy_(gq.to(BF16))
             dkvv[:, :, k_slot].copy_(gk.to(BF16))
             dkvv[:, :, v_slot].copy_(gv.to(BF16))
         if same:
-            return dq_src, None, None, None, None, None, None, None, None, None, None, None, None
+            return (dq_src,) + (None,) * 13
         if hold is not None and ctx.kv_idx != 0:
             dkv_src = None                 # slots written; the first caller returns the buffer
-        return dq_src, dkv_src, None, None, None, None, None, None, None, None, None, None, None
+        return (dq_src, dkv_src) + (None,) * 12
 
 
 def _attn_views(q_src, kv_src, H, nq, nkv, q_slot, tm):
@@ -1753,12 +1782,16 @@ def _attn_views(q_src, kv_src, H, nq, nkv, q_slot, tm):
 
 
 def self_attention(qkv: torch.Tensor, heads: int, causal: bool = False,
-                   kv_len: Optional[torch.Tensor] = None, drop: Optional[float] = None) -> torch.Tensor:
+                   kv_len: Optional[torch.Tensor] = None, drop: Optional[float] = None,
+                   rope: Optional[torch.Tensor] = None) -> torch.Tensor:
     """qkv: [B,S,3*H*64] packed projection output -> [B,S,H*64]. drop:
     dropout probability on the softmax probabilities (quantised to 1/256;
-    needs an installed record, see ``set_dropout``)."""
+    needs an installed record, see ``set_dropout``). rope: a ``rope_table``
+    of at least S rows -- rotary position embedding of q and k (pairs
+    (j, j + 32), angle = token index * 10000^(-j/32)) inside the attention
+    kernels, forward and backward."""
     qkv = qkv.contiguous()
-    return _Attn.apply(qkv, qkv, heads, 0, 3, 1, 2, 3, causal, kv_len, None, False, _attn_drop_args(drop))
+    return _Attn.apply(qkv, qkv, heads, 0, 3, 1, 2, 3, causal, kv_len, None, False, _attn_drop_args(drop), rope)
 
 
 def cross_attention(q: torch.Tensor, kv: torch.Tensor, heads: int,
