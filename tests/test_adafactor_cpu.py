@@ -48,7 +48,7 @@ def test_request_validation(tmp_path):
     cfg = bench.make_cfg("dlas-gpu", "tiresias", 2, 3, "none", [0.05, 0.25, 1.0], False)
     ctrl = Controller(cfg, [], 2, 0.05, spool=Spool(str(tmp_path / "spool")), clock=VirtualClock())
     base = {"model": "transformer", "iterations": 2, "job_id": "x", "opt_dtype": "factored"}
-    assert ctrl._validate(base)[-2] == "factored"
+    assert ctrl._validate(base)[-1]["opt_dtype"] == "factored"
     with pytest.raises(ValueError, match="adam"):
         ctrl._validate(dict(base, model="vgg16"))
     with pytest.raises(ValueError, match="trust_ratio"):

@@ -232,7 +232,7 @@ def test_bad_trust_ratio_is_rejected_not_fatal(tmp_path):
     ctrl.ddp_shard = True
     with pytest.raises(ValueError, match="ddp_shard"):
         ctrl._validate(dict(base, job_id="x", num_gpu=2, trust_ratio=0.1))
-    assert ctrl._validate(dict(base, job_id="x", num_gpu=1, trust_ratio=0.1))[-1] == 0.1
+    assert ctrl._validate(dict(base, job_id="x", num_gpu=1, trust_ratio=0.1))[-1]["trust_ratio"] == 0.1
 
 
 def test_worker_sets_it_per_job_on_new_and_pooled_trainers():

@@ -45,6 +45,7 @@ from ..core.job import Job, JobSpec, JobState
 from ..engine.sim import Simulator
 from ..metrics.logger import MetricsLogger
 from ..parallel.gang import GangRegistry, abort_comm, comm_failed, create_gang_comm, vnode_parts
+from .knobs import KNOBS, STRUCTURAL, check_knob, check_sharded, check_together, wire
 from .trainer import Trainer
 
 # nominal per-iteration seconds on one MI355X (tools/bench_models.py,
@@ -516,11 +517,7 @@ class Controller:
         now = self.now()
         for req in self.spool.poll():
             try:
-                jid, model, g, iters, batch, clip, drop, adrop, odt, eta = self._validate(req)
-                norm = self._validate_norm(req, model)
-                card = self._validate_cardinality(req, model)
-                se = self._validate_se_ratio(req, model)
-                pos = self._validate_pos(req, model)
+                jid, model, g, iters, batch, knobs = self._validate(req)
                 why = ""
             except (ValueError, TypeError, OverflowError) as e:
                 jid = str(req.get("job_id") or "")
@@ -531,10 +528,8 @@ class Controller:
                     self.log.decision(now, "reject", jid or "?", reason=why)
                 continue
             spec = JobSpec(job_id=jid, submit_time=now, duration=iters * self._iter_est(model, g),
-                           num_gpu=g, model=model, iterations=iters, opt_dtype=odt)
-            self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, grad_clip=clip,
-                                        dropout=drop, attn_dropout=adrop, opt_dtype=odt, trust_ratio=eta,
-                                        norm=norm, cardinality=card, se_ratio=se, pos=pos)
+                           num_gpu=g, model=model, iterations=iters, opt_dtype=knobs["opt_dtype"])
+            self.rjobs[jid] = ReplayJob(spec=spec, model=model, iterations=iters, batch=batch, **knobs)
             self.done_iters[jid] = 0
             self.sched.submit(JobSpec(**{**spec.__dict__, "duration": float(iters)}))
             self.spool.resolve(req, True)
@@ -543,8 +538,8 @@ class Controller:
 
     def _validate(self, req: dict):
         """Untrusted spool request -> (job_id, model, num_gpu, iterations,
-        batch, grad_clip, dropout, attn_dropout, opt_dtype, trust_ratio); raises
-        ValueError with the rejection reason."""
+        batch, knobs), ``knobs`` the per-job training knobs by name
+        (executor/knobs.py); raises ValueError with the rejection reason."""
         from ..models import MODELS
 
         jid = req.get("job_id")
@@ -577,87 +572,12 @@ class Controller:
                 raise ValueError("iterations/duration must be positive")
             iters = max(1, int(round(float(dur) / self._iter_est(model, g))))
         iters = pos_int("iterations", iters)
-        clip = req.get("grad_clip")
-        if clip is not None:
-            if isinstance(clip, bool) or not isinstance(clip, (int, float)) or not clip > 0 or clip == float("inf"):
-                raise ValueError(f"grad_clip must be a finite number > 0, got {clip!r}")
-            clip = float(clip)
-            if self.ddp_shard and g > 1:
-                raise ValueError("grad_clip is not supported for a multi-GPU job under ddp_shard")
-        drop = req.get("dropout")
-        if drop is not None:
-            if (isinstance(drop, bool) or not isinstance(drop, (int, float)) or not 0 <= drop < 1
-                    or round(drop * 65536) >= 65536):
-                raise ValueError(f"dropout must be a number p with 0 <= p < 1 (quantised to 1/65536), got {drop!r}")
-            drop = float(drop)
-        adrop = req.get("attn_dropout")
-        if adrop is not None:
-            if (isinstance(adrop, bool) or not isinstance(adrop, (int, float)) or not 0 <= adrop < 1
-                    or round(adrop * 256) >= 256):
-                raise ValueError(f"attn_dropout must be a number p with 0 <= p < 1 (quantised to 1/256), got {adrop!r}")
-            adrop = float(adrop)
-        odt = req.get("opt_dtype")
-        if odt is not None and (not isinstance(odt, str) or odt not in ("fp32", "bf16", "factored")):
-            raise ValueError(f"opt_dtype must be 'fp32' or 'bf16', or 'factored' for an adam model, got {odt!r}")
-        if odt == "factored":
-            from ..models import MODELS
-
-            if model in MODELS and MODELS[model].opt != "adam":
-                raise ValueError(f"opt_dtype 'factored' (Adafactor) needs an adam model, {model!r} is not one")
-            if self.ddp_shard and g > 1:
-                raise ValueError("opt_dtype 'factored' is not supported for a multi-GPU job under ddp_shard")
-        eta = req.get("trust_ratio")
-        if eta is not None:
-            if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta > 0 or eta == float("inf"):
-                raise ValueError(f"trust_ratio must be a finite number > 0, got {eta!r}")
-            eta = float(eta)
-            if self.ddp_shard and g > 1:
-                raise ValueError("trust_ratio is not supported for a multi-GPU job under ddp_shard")
-            if odt in ("bf16", "factored"):
-                raise ValueError(f"trust_ratio is not supported with opt_dtype {odt!r}")
-        return jid, model, g, iters, batch, clip, drop, adrop, odt, eta
-
-    @staticmethod
-    def _validate_norm(req: dict, model: str) -> Optional[str]:
-        """The request's ``norm`` key (absent / null: None, the model's own
-        normalisation); ValueError for a value that is not one or a model
-        without BatchNorm layers."""
-        from .trainer import check_norm
-
-        norm = req.get("norm")
-        if norm is not None:
-            check_norm(model, norm)
-        return norm
-
-    @staticmethod
-    def _validate_cardinality(req: dict, model: str) -> Optional[int]:
-        """The request's ``cardinality`` key (absent / null: None, the plain
-        model); ValueError for a value that is not one or a model without a
-        bottleneck to group."""
-        from .trainer import check_cardinality
-
-        return check_cardinality(model, req.get("cardinality"))
-
-    @staticmethod
-    def _validate_se_ratio(req: dict, model: str) -> Optional[int]:
-        """The request's ``se_ratio`` key (absent / null: None, no SE blocks);
-        ValueError for a value that is not one or a model without a
-        bottleneck to gate."""
-        from .trainer import check_se_ratio
-
-        return check_se_ratio(model, req.get("se_ratio"))
-
-    @staticmethod
-    def _validate_pos(req: dict, model: str) -> Optional[str]:
-        """The request's ``pos`` key (absent / null: None, the model's own
-        position encoding); ValueError for a value that is not one or a model
-        without self-attention."""
-        from .trainer import check_pos
-
-        pos = req.get("pos")
-        if pos is not None:
-            check_pos(model, pos)
-        return pos
+        # an absent / null key stays None: the job runs with the model's own value
+        knobs = {k: None if req.get(k) is None else check_knob(k, model, req[k]) for k in KNOBS}
+        check_together(knobs)
+        if self.ddp_shard and g > 1:
+            check_sharded(knobs)
+        return jid, model, g, iters, batch, knobs
 
     def status(self) -> dict:
         s = self.sched
@@ -718,17 +638,8 @@ class Controller:
                 rj = self.rjobs[j.job_id]
                 act = {"op": "start", "job": j.job_id, "ranks": ranks, "model": rj.model,
                        "iters": max(0, rj.iterations - self.done_iters[j.job_id]),
-                       "batch": rj.batch, "grad_clip": rj.grad_clip, "dropout": rj.dropout,
-                       "attn_dropout": rj.attn_dropout, "opt_dtype": rj.opt_dtype, "trust_ratio": rj.trust_ratio,
+                       "batch": rj.batch, **wire({k: getattr(rj, k) for k in KNOBS}),
                        "seed": int(j.job_id) if j.job_id.isdigit() else zlib.crc32(j.job_id.encode()) % 100000}
-                if rj.norm is not None:        # (a job that did not ask: the action as it always was)
-                    act["norm"] = rj.norm
-                if rj.cardinality is not None:
-                    act["cardinality"] = rj.cardinality
-                if rj.se_ratio is not None:
-                    act["se_ratio"] = rj.se_ratio
-                if rj.pos is not None:
-                    act["pos"] = rj.pos
                 if old is None and j.job_id in self.from_snap:
                     step, path = self.from_snap.pop(j.job_id)
                     act["source"] = "snapshot"
@@ -966,25 +877,15 @@ class Worker:
 
     @staticmethod
     def _pool_key(act) -> tuple:
-        """Warm-pool key of a start action: what fixes a trainer's buffers.
-        The optimizer-state format does (bf16 state buffers cannot serve a
-        fp32-state job, nor the reverse), so a bf16- or factored-state job's key carries it;
-        the per-job setters (clip, dropouts, trust ratio) are not part of the key.
-        A GroupNorm job's model has other layers and no running statistics, so
-        its key carries ``norm`` too, a ResNeXt job's its ``cardinality`` and an
-        SE job's its ``se_ratio``. A rotary-position job has the same buffers
-        but another forward (and another captured graph): its key carries
-        ``pos``."""
+        """Warm-pool key of a start action: what fixes a trainer's model and
+        buffers. The structural knobs do (executor/knobs.py: each adds its
+        token unless the job runs with the knob's default); the per-job
+        setters (clip, dropouts, trust ratio) are not part of the key."""
         key = (act["model"], act.get("batch"), tuple(act["ranks"]))
-        if act.get("opt_dtype") in ("bf16", "factored"):
-            key += (act["opt_dtype"],)
-        if act.get("norm") == "group":
-            key += ("norm=group",)
-        if act.get("cardinality") is not None:
-            key += (f"cardinality={act['cardinality']}",)
-        if act.get("se_ratio") is not None:
-            key += (f"se_ratio={act['se_ratio']}",)
-        return key + ("pos=rope",) if act.get("pos") == "rope" else key
+        for k in STRUCTURAL:
+            if act.get(k.name) not in (None, k.default):
+                key += (k.token.format(act[k.name]),)
+        return key
 
     def _make_trainer(self, act, init: bool = True) -> Trainer:
         ranks = tuple(act["ranks"])
@@ -1000,40 +901,29 @@ class Worker:
         want = self.use_graph and len(ranks) == 1 and (long_job or self.pool_cap > 0)
         free = self.pool.get(key)
         if free:
-            # the key carries the state format; a pooled trainer of the other
-            # format under it would run the wrong kernels silently
-            want_dt = act.get("opt_dtype") or "fp32"
-            if free[-1].opt_dtype != want_dt:
-                raise RuntimeError(f"warm pool {key}: a {free[-1].opt_dtype}-state trainer is pooled under the "
-                                   f"key of a {want_dt}-state job")
-            if free[-1].norm != (act.get("norm") or "batch"):
-                raise RuntimeError(f"warm pool {key}: a norm={free[-1].norm} trainer is pooled under the key of a "
-                                   f"norm={act.get('norm') or 'batch'} job")
-            if free[-1].cardinality != act.get("cardinality"):
-                raise RuntimeError(f"warm pool {key}: a cardinality={free[-1].cardinality} trainer is pooled under "
-                                   f"the key of a cardinality={act.get('cardinality')} job")
-            if free[-1].se_ratio != act.get("se_ratio"):
-                raise RuntimeError(f"warm pool {key}: a se_ratio={free[-1].se_ratio} trainer is pooled under "
-                                   f"the key of a se_ratio={act.get('se_ratio')} job")
-            if free[-1].pos != (act.get("pos") or "sinusoid"):
-                raise RuntimeError(f"warm pool {key}: a pos={free[-1].pos} trainer is pooled under the key of a "
-                                   f"pos={act.get('pos') or 'sinusoid'} job")
+            # the key carries the structural knobs (the state format among
+            # them); a pooled trainer of another value under it would run the
+            # wrong kernels silently
+            for k in STRUCTURAL:
+                have = getattr(free[-1], k.name)
+                need = k.default if act.get(k.name) is None else act[k.name]
+                if have != need:
+                    raise RuntimeError(f"warm pool {key}: a {k.label.format(have)} trainer is pooled under the "
+                                       f"key of a {k.label.format(need)} job")
             self.pool_hits += 1
             t = free.pop().reset(act["seed"], data_seed, init=init)
-            t.set_grad_clip(act.get("grad_clip"))    # per job, not part of the pool key
-            t.set_dropout(act.get("dropout"))        # likewise (a change re-captures the graph)
-            t.set_attn_dropout(act.get("attn_dropout"))
-            t.set_trust_ratio(act.get("trust_ratio"))    # per job too: its buffers are a few KiB
+            for k in KNOBS.values():
+                if not k.fixes:
+                    # per job, not part of the pool key (a changed dropout
+                    # re-captures the graph; the trust ratio's buffers are a few KiB)
+                    getattr(t, "set_" + k.name)(act.get(k.name))
             self._bind(t, ranks)
             if want and not t.use_graph and t.ddp is None:
                 t.enable_graph()
             return t
         t = Trainer(act["model"], self.device, batch=act.get("batch"), group=self._group(ranks),
                     seed=act["seed"], data_seed=data_seed, use_graph=want, ddp_shard=self.ddp_shard,
-                    ddp_wire=self.ddp_wire, grad_clip=act.get("grad_clip"), dropout=act.get("dropout"),
-                    attn_dropout=act.get("attn_dropout"), opt_dtype=act.get("opt_dtype"),
-                    trust_ratio=act.get("trust_ratio"), norm=act.get("norm"),
-                    cardinality=act.get("cardinality"), se_ratio=act.get("se_ratio"), pos=act.get("pos"))
+                    ddp_wire=self.ddp_wire, **{k: act.get(k) for k in KNOBS})
         t.pool_key = key
         return t
 
@@ -1372,10 +1262,8 @@ class Worker:
                 if self.rank in ranks and self.rank in old:
                     t = self.trainers[a["job"]]
                     t.rebind(self._group(ranks))
-                    # (the trainer's own state format, whatever the action carries)
-                    t.pool_key = self._pool_key(dict(a, opt_dtype=t.opt_dtype, norm=t.norm,
-                                                        cardinality=t.cardinality, se_ratio=t.se_ratio,
-                                                        pos=t.pos))
+                    # (the trainer's own structural values, whatever the action carries)
+                    t.pool_key = self._pool_key(dict(a, **{k.name: getattr(t, k.name) for k in STRUCTURAL}))
                 elif self.rank in ranks:
                     self._bind(self.trainers[a["job"]], ranks)
                 if self.rank in ranks and "step" in a:

@@ -34,6 +34,7 @@ from ..metrics.logger import MetricsLogger
 from ..parallel.gang import ring_exchange_bytes, vnode_parts
 from ..profiler.skew import model_profile
 from .cluster_runtime import NOMINAL_ITER_S, Controller, ReplayJob
+from .knobs import KNOBS
 
 
 class ProtocolError(AssertionError):
@@ -84,11 +85,10 @@ class FakeCluster:
         self.held: Dict[str, Tuple[int, ...]] = {}      # job -> ranks holding its state in HBM
         self.spilled: Set[str] = set()
         self.model: Dict[str, str] = {}
-        self.odt: Dict[str, Optional[str]] = {}      # job -> optimizer-state format (start action's opt_dtype)
-        self.norm: Dict[str, Optional[str]] = {}     # job -> normalisation it was started with (start action's norm)
-        self.card: Dict[str, Optional[int]] = {}     # job -> ResNeXt cardinality it was started with
-        self.se: Dict[str, Optional[int]] = {}       # job -> Squeeze-and-Excitation ratio it was started with
-        self.pos: Dict[str, Optional[str]] = {}      # job -> position encoding it was started with
+        # knob name -> job -> the value the job's last start action carried
+        self.knobs: Dict[str, Dict[str, object]] = {k: {} for k in KNOBS}
+        # (the names under which the knob suites read four of them)
+        self.norm, self.card, self.se, self.pos = (self.knobs[k] for k in ("norm", "cardinality", "se_ratio", "pos"))
         self.groups: Set[Tuple[int, ...]] = set()
         self.stats = {"p2p_bytes": 0.0, "spill_bytes": 0.0, "restore_bytes": 0.0, "starts": 0,
                       "resident_resumes": 0, "rounds": 0}
@@ -159,58 +159,37 @@ class FakeCluster:
                 if job in self.spilled:
                     raise ProtocolError(f"consolidate of {job} after its spill")
                 w = len(ranks)
-                b = _state_bytes(self.model[job], self.odt.get(job)) * (w - 1) / w
+                b = _state_bytes(self.model[job], self.knobs["opt_dtype"][job]) * (w - 1) / w
                 charge(ranks, b / self.xgmi)
                 self.stats["consolidate_bytes"] = self.stats.get("consolidate_bytes", 0.0) + b * w
             elif op == "spill":
                 if job not in self.held or job in self.spilled:
                     raise ProtocolError(f"spill of job {job} that is not resident")
-                b = _state_bytes(self.model[job], self.odt.get(job))
+                b = _state_bytes(self.model[job], self.knobs["opt_dtype"][job])
                 charge(self.held[job], b / self.host)
                 self.stats["spill_bytes"] += b * len(self.held[job])
                 self.spilled.add(job)
             elif op == "start":
-                # (the per-job recipe keys grad_clip / dropout / attn_dropout /
-                # trust_ratio change no cost in the world model: accepted and ignored;
-                # opt_dtype sizes the state that spills and moves)
                 ranks = tuple(a["ranks"])
                 if len(ranks) > 1 and ranks not in self.groups:
                     raise ProtocolError(f"gang {job} started on {ranks} without a communicator")
                 self.model[job] = a["model"]
-                self.odt[job] = a.get("opt_dtype")
-                # norm fixes a job's model: every start of a job carries the
-                # same one (GroupNorm adds no state and no cost to the world model)
-                if a.get("norm") not in (None, "batch", "group"):
-                    raise ProtocolError(f"start of {job} with norm {a.get('norm')!r}")
-                if job in self.held and self.norm.get(job) != a.get("norm"):
-                    raise ProtocolError(f"start of {job} with norm {a.get('norm')!r}, its state was built "
-                                        f"with {self.norm.get(job)!r}")
-                self.norm[job] = a.get("norm")
-                # cardinality fixes a job's model the same way
-                card = a.get("cardinality")
-                if card is not None and (isinstance(card, bool) or not isinstance(card, int) or card % 4
-                                         or not 4 <= card <= 64):
-                    raise ProtocolError(f"start of {job} with cardinality {card!r}")
-                if job in self.held and self.card.get(job) != card:
-                    raise ProtocolError(f"start of {job} with cardinality {card!r}, its state was built with "
-                                        f"{self.card.get(job)!r}")
-                self.card[job] = card
-                # and so does se_ratio
-                se = a.get("se_ratio")
-                if se is not None and (isinstance(se, bool) or not isinstance(se, int) or se not in (4, 8, 16, 32)):
-                    raise ProtocolError(f"start of {job} with se_ratio {se!r}")
-                if job in self.held and self.se.get(job) != se:
-                    raise ProtocolError(f"start of {job} with se_ratio {se!r}, its state was built with "
-                                        f"{self.se.get(job)!r}")
-                self.se[job] = se
-                # pos fixes a job's forward: no state, no cost to the world
-                # model, but every start of a job carries the same one
-                if a.get("pos") not in (None, "sinusoid", "rope"):
-                    raise ProtocolError(f"start of {job} with pos {a.get('pos')!r}")
-                if job in self.held and self.pos.get(job) != a.get("pos"):
-                    raise ProtocolError(f"start of {job} with pos {a.get('pos')!r}, its state was built with "
-                                        f"{self.pos.get(job)!r}")
-                self.pos[job] = a.get("pos")
+                # the per-job knobs (executor/knobs.py) carry legal values; of
+                # them only opt_dtype changes a cost in the world model (it
+                # sizes the state that spills and moves)
+                for k in KNOBS.values():
+                    v = a.get(k.name)
+                    try:
+                        if v is not None:
+                            k.value(v)
+                    except ValueError:
+                        raise ProtocolError(f"start of {job} with {k.name} {v!r}") from None
+                    # a structural knob fixes a job's model or buffers: every
+                    # start of a job carries the same one
+                    was = self.knobs[k.name].get(job)
+                    if k.fixes and job in self.held and was != v:
+                        raise ProtocolError(f"start of {job} with {k.name} {v!r}, its state was built with {was!r}")
+                    self.knobs[k.name][job] = v
                 src = a["source"]
                 b = _state_bytes(a["model"], a.get("opt_dtype"))
                 if src == "fresh":

@@ -21,12 +21,11 @@ Request schema (JSON)::
      "opt_dtype": null,             # optimizer-state format, "fp32", "bf16" or "factored" (null = fp32)
      "trust_ratio": null}           # layer-wise trust coefficient > 0: LARS (sgd models) / LAMB (adam models)
 
-A job that asks for ``--norm`` carries one more key, ``"norm": "batch" |
-"group"`` (ResNet models); a request without it is written as before. The
-same holds for ``--cardinality``: ``"cardinality": G`` (ResNeXt, ResNet models)
-and for ``--se-ratio``: ``"se_ratio": R`` (Squeeze-and-Excitation, ResNet models)
-and for ``--pos``: ``"pos": "sinusoid" | "rope"`` (position encoding, Transformer
-models).
+The keys from ``grad_clip`` on are the per-job training knobs: the rows of
+``executor/knobs.py::KNOBS``, which hold their legal values and the models
+they apply to. A job that asks for a ``sparse`` knob there (``norm``,
+``cardinality``, ``se_ratio``, ``pos``) carries one more key, e.g. ``"norm":
+"group"``; a request without it is written as before.
 """
 from __future__ import annotations
 
@@ -35,6 +34,8 @@ import os
 import time
 import uuid
 from typing import Dict, List, Optional
+
+from .knobs import wire
 
 
 def _atomic_write(path: str, obj) -> None:
@@ -53,26 +54,14 @@ class Spool:
     # ------------------------------------------------------------ client side
     def submit(self, model: str, num_gpu: int = 1, iterations: Optional[int] = None,
                duration: Optional[float] = None, job_id: Optional[str] = None,
-               batch: Optional[int] = None, grad_clip: Optional[float] = None,
-               dropout: Optional[float] = None, attn_dropout: Optional[float] = None,
-               opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
-               norm: Optional[str] = None, cardinality: Optional[int] = None,
-               se_ratio: Optional[int] = None, pos: Optional[str] = None) -> str:
+               batch: Optional[int] = None, **knobs) -> str:
+        """``knobs``: the job's per-job training knobs by name (executor/knobs.py);
+        TypeError for a name that is not one."""
         if iterations is None and duration is None:
             raise ValueError("give iterations or duration")
         jid = job_id or f"sub-{time.time_ns()}-{os.getpid()}"
         req = {"job_id": jid, "model": model, "num_gpu": int(num_gpu), "iterations": iterations,
-               "duration": duration, "batch": batch, "grad_clip": grad_clip, "dropout": dropout,
-               "attn_dropout": attn_dropout, "opt_dtype": opt_dtype,
-               "trust_ratio": trust_ratio, "submitted_wall": time.time()}
-        if norm is not None:
-            req["norm"] = norm
-        if cardinality is not None:
-            req["cardinality"] = cardinality
-        if se_ratio is not None:
-            req["se_ratio"] = se_ratio
-        if pos is not None:
-            req["pos"] = pos
+               "duration": duration, "batch": batch, **wire(knobs), "submitted_wall": time.time()}
         _atomic_write(os.path.join(self.root, "incoming", f"{jid}.json"), req)
         return jid
 

@@ -20,6 +20,8 @@ from ..ops import functional as Fx
 from ..ops.arena import Arena, _padded, adafactor_tables, factored_shape, trust_tile_table
 from ..parallel.ddp import GradBucketer
 from ..parallel.gang import comm_rank, comm_size
+from .knobs import KNOBS, STRUCTURAL, check_knob, check_sharded, check_together
+from .knobs import check_cardinality, check_pos, check_se_ratio  # noqa: F401 (importable from here as before)
 
 
 class Trainer:
@@ -32,65 +34,20 @@ class Trainer:
                  opt_dtype: Optional[str] = None, trust_ratio: Optional[float] = None,
                  norm: Optional[str] = None, cardinality: Optional[int] = None,
                  se_ratio: Optional[int] = None, pos: Optional[str] = None):
+        # the knob keywords by name. FIRST statement: locals() holds exactly
+        # the parameters here, and every knob of the table must be one of them
+        asked = {k: v for k, v in locals().items() if k in KNOBS}
         self.model_name = model
         self.spec = MODELS[model]
-        # normalisation of a CNN job (README "GroupNorm"): "group" builds the
-        # model with GroupNorm in place of every BatchNorm. It changes the
-        # model's structure and buffers, so it is set at construction (and is
-        # part of the worker's warm-pool key), not by a per-job setter
-        self.norm = check_norm(model, self.spec.norm if norm is None else norm)
-        # ResNeXt cardinality of a ResNet job (README "ResNeXt"): G builds every
-        # bottleneck with a G-group 3x3 conv on the grouped conv kernels. Like
-        # norm it fixes the model's structure: set at construction, part of
-        # the worker's warm-pool key, no per-job setter
-        self.cardinality = check_cardinality(model, self.spec.cardinality if cardinality is None else cardinality)
-        # Squeeze-and-Excitation ratio of a ResNet job (README "SE blocks"): r
-        # adds an SE block (four parameters, the se.hip kernels) to every
-        # bottleneck. Structure again: construction, pool key, no setter
-        self.se_ratio = check_se_ratio(model, self.spec.se_ratio if se_ratio is None else se_ratio)
-        # position encoding of a Transformer job (README "rotary position embeddings"):
-        # "rope" rotates Q and K inside the self-attention kernels in place of
-        # the additive table. No parameter moves, but the model's forward is
-        # another one: construction, pool key, no setter
-        self.pos = check_pos(model, self.spec.pos if pos is None else pos)
-        if opt_dtype is None:
-            opt_dtype = self.spec.opt_dtype
-        if opt_dtype not in (None, "fp32", "bf16", "factored"):
-            raise ValueError(f"opt_dtype must be 'fp32', 'bf16' or 'factored', got {opt_dtype!r}")
-        # format of the optimizer state (README "bf16 optimizer state",
-        # "Factored optimizer state"). It fixes the buffer types, so it is set
-        # at construction (and is part of the worker's warm-pool key), not by
-        # a per-job setter
-        self.opt_dtype = opt_dtype or "fp32"
-        if self.opt_dtype == "factored":
-            if self.spec.opt != "adam":
-                raise ValueError(f"opt_dtype='factored' is Adafactor, which replaces Adam: {model!r} is an "
-                                 f"{self.spec.opt!r} model")
-            if ddp_shard and group is not None and comm_size(group) > 1:
-                raise ValueError("opt_dtype='factored' with ddp_shard is not supported: a sharded member holds "
-                                 "only slices of the rows its row and column means run over")
-            if trust_ratio is not None or self.spec.trust_ratio is not None:
-                raise ValueError("opt_dtype='factored' with trust_ratio is not supported: LAMB's ratio is "
-                                 "defined over Adam's update")
-        if self.opt_dtype == "bf16" and ddp_shard and group is not None and comm_size(group) > 1:
-            raise ValueError("opt_dtype='bf16' with ddp_shard is not supported: the sharded gang's slice "
-                             "launches and state all-gather are fp32-state only")
-        if dropout is None:
-            dropout = self.spec.dropout
-        if attn_dropout is None:
-            attn_dropout = self.spec.attn_dropout
-        if grad_clip is None:
-            grad_clip = self.spec.clip
-        if grad_clip is not None and ddp_shard and group is not None and comm_size(group) > 1:
-            raise ValueError("grad_clip with ddp_shard is not supported: a sharded gang's global norm needs "
-                             "the replicated tails counted once")
-        if trust_ratio is None:
-            trust_ratio = self.spec.trust_ratio
-        if trust_ratio is not None:
-            _check_trust_ratio(trust_ratio)
-            if ddp_shard and group is not None and comm_size(group) > 1:
-                raise ValueError("trust_ratio with ddp_shard is not supported: a sharded member holds only "
-                                 "slices of the segments its norms run over")
+        # the per-job knobs (executor/knobs.py): what the caller asked for,
+        # else the ModelSpec's value, else the knob's default
+        knobs = {k.name: check_knob(k.name, model, getattr(self.spec, k.spec_field) if asked[k.name] is None
+                                    else asked[k.name]) for k in KNOBS.values()}
+        check_together(knobs)
+        if ddp_shard and group is not None and comm_size(group) > 1:
+            check_sharded(knobs)
+        for k in STRUCTURAL:                # (the per-job ones go through their setters below)
+            setattr(self, k.name, knobs[k.name])
         self.device = torch.device(device)
         if self.device.type == "cuda":
             _lib.load(required=True)
@@ -98,14 +55,9 @@ class Trainer:
         self.seed = seed
         self.arena = Arena(self.device, seed=seed)
         mk = dict(model_kwargs or {})
-        if self.norm == "group":
-            mk["norm"] = "group"
-        if self.cardinality is not None:
-            mk["cardinality"] = self.cardinality
-        if self.se_ratio is not None:
-            mk["se_ratio"] = self.se_ratio
-        if self.pos == "rope":
-            mk["pos"] = "rope"
+        for k in STRUCTURAL:
+            if k.fixes == "model" and knobs[k.name] != k.default:
+                mk[k.name] = knobs[k.name]
         self.model = make_model(model, self.arena, **mk)
         self.arena.materialize()
         n = self.arena.numel
@@ -160,14 +112,14 @@ class Trainer:
         self._clip = None               # device clip record (optim.hip): scale, norm, 2 counters
         self._clip_part = None          # grad_sumsq's per-block fp64 partials
         self._clip_host = [1.0, 0.0, 0, 0]   # the same four words on the CPU path
-        self.set_grad_clip(grad_clip)
+        self.set_grad_clip(knobs["grad_clip"])
         # layer-wise trust ratio (set_trust_ratio: LARS for an sgd job, LAMB
         # for an adam job); None = off, nothing allocated or launched
         self.trust_ratio: Optional[float] = None
         self._tr = None                 # device (tiles, seg_first, partials, ratios) of lars_step / lamb_step
         self._tr_host: Dict[str, tuple] = {}   # the last step's ratios on the CPU path
         self._tr_stepped = False        # an optimizer step ran with the knob on since reset
-        self.set_trust_ratio(trust_ratio)
+        self.set_trust_ratio(knobs["trust_ratio"])
         # training dropout (set_dropout) and attention-probability dropout
         # (set_attn_dropout); None = off, and with both off nothing is
         # allocated or launched. They share the record and its one advance
@@ -175,8 +127,8 @@ class Trainer:
         self.attn_dropout: Optional[float] = None
         self._drop_rec = None           # int32[4] {seed, stream, step, 0} on the trainer's device
         self._drop_at = None            # (seed, stream, step) the record holds, tracked on the host
-        self.set_dropout(dropout)
-        self.set_attn_dropout(attn_dropout)
+        self.set_dropout(knobs["dropout"])
+        self.set_attn_dropout(knobs["attn_dropout"])
         # weight init and the synthetic batch were queued on the stream that
         # built the trainer; a step issued from another stream (GPU sharing
         # runs each job on its own stream) must wait for them first
@@ -328,12 +280,9 @@ class Trainer:
         A non-sharded gang needs no extra collective: after the all-reduce
         every member holds the same gradient and computes the same scale."""
         if v is not None:
-            v = float(v)
-            if not (v > 0.0 and v != float("inf")):
-                raise ValueError(f"grad_clip must be a finite number > 0, got {v}")
+            v = KNOBS["grad_clip"].value(float(v))    # (a caller in the process may pass anything float() takes)
             if self.ddp is not None and self.ddp.shard:
-                raise ValueError("grad_clip with ddp_shard is not supported: a sharded gang's global norm "
-                                 "needs the replicated tails counted once")
+                check_sharded({"grad_clip": v})
             if self.device.type == "cuda" and self._clip is None:
                 T = _lib.ops()
                 self._clip = torch.zeros(4, dtype=torch.float32, device=self.device)
@@ -382,16 +331,10 @@ class Trainer:
         all-reduce every member holds the same gradient and computes the same
         ratios."""
         if v is not None:
-            v = _check_trust_ratio(v)
+            v = KNOBS["trust_ratio"].value(v)
             if self.ddp is not None and self.ddp.shard:
-                raise ValueError("trust_ratio with ddp_shard is not supported: a sharded member holds only "
-                                 "slices of the segments its norms run over")
-            if self.opt_dtype == "bf16":
-                raise ValueError("trust_ratio with opt_dtype='bf16' is not supported: LAMB's second pass would "
-                                 "take the weights from the rounded moments")
-            if self.opt_dtype == "factored":
-                raise ValueError("trust_ratio with opt_dtype='factored' is not supported: LAMB's ratio is "
-                                 "defined over Adam's update")
+                check_sharded({"trust_ratio": v})
+            check_together({"trust_ratio": v, "opt_dtype": self.opt_dtype})
             if self.device.type == "cuda" and self._tr is None:
                 A = self.arena
                 segs = [(p.offset, _padded(p.numel)) for p in A.decay_segments()]
@@ -905,14 +848,8 @@ class Trainer:
     def rebind(self, group) -> None:
         """Move the job to a new DDP gang (after a preemption resumed it on
         different GPUs): new communicator, fresh bucketer."""
-        if self.grad_clip is not None and self.ddp_shard and group is not None and comm_size(group) > 1:
-            raise ValueError("grad_clip with ddp_shard is not supported")
-        if self.opt_dtype == "bf16" and self.ddp_shard and group is not None and comm_size(group) > 1:
-            raise ValueError("opt_dtype='bf16' with ddp_shard is not supported")
-        if self.trust_ratio is not None and self.ddp_shard and group is not None and comm_size(group) > 1:
-            raise ValueError("trust_ratio with ddp_shard is not supported")
-        if self.opt_dtype == "factored" and self.ddp_shard and group is not None and comm_size(group) > 1:
-            raise ValueError("opt_dtype='factored' with ddp_shard is not supported")
+        if self.ddp_shard and group is not None and comm_size(group) > 1:
+            check_sharded({k: getattr(self, k) for k in KNOBS})
         # sharded state survives only a re-created communicator over the SAME
         # rank set (same member positions); anything else needs consolidate()
         dirty = self.state_sharded
@@ -966,69 +903,6 @@ class Trainer:
         self._g_loss = None
         self.last_loss = None                    # may alias the graph's output
         self.arena.on_grad_ready = None
-
-
-def check_norm(model: str, norm) -> str:
-    """The normalisation a job of ``model`` runs with ("batch" when ``norm`` is
-    None); ValueError for a value that is not one, or for a model that has no
-    BatchNorm layers to replace."""
-    if norm is None:
-        return "batch"
-    if not isinstance(norm, str) or norm not in ("batch", "group"):
-        raise ValueError(f"norm must be 'batch' or 'group', got {norm!r}")
-    if norm not in getattr(MODELS[model].builder, "norms", ()):
-        raise ValueError(f"norm={norm!r}: {model!r} has no BatchNorm layers (the knob is for the ResNet models)")
-    return norm
-
-
-def check_cardinality(model: str, v) -> Optional[int]:
-    """The ResNeXt cardinality a job of ``model`` runs with (None: the plain
-    model); ValueError for a value that is not an integer multiple of 4 in
-    [4, 64], or for a model whose builder has no bottleneck to group."""
-    if v is None:
-        return None
-    from ..models.cnn import check_cardinality_value
-
-    check_cardinality_value(v)
-    if not getattr(MODELS[model].builder, "cardinalities", False):
-        raise ValueError(f"cardinality={v!r}: {model!r} has no bottleneck 3x3 conv to group (the knob is for the "
-                         "ResNet models)")
-    return v
-
-
-def check_se_ratio(model: str, v) -> Optional[int]:
-    """The Squeeze-and-Excitation ratio a job of ``model`` runs with (None: no
-    SE blocks); ValueError for a value that is not one of the integers 4, 8,
-    16, 32, or for a model whose builder has no bottleneck to gate."""
-    if v is None:
-        return None
-    from ..models.cnn import check_se_ratio_value
-
-    check_se_ratio_value(v)
-    if not getattr(MODELS[model].builder, "se_ratios", False):
-        raise ValueError(f"se_ratio={v!r}: {model!r} has no bottleneck to put an SE block on (the knob is for the "
-                         "ResNet models)")
-    return v
-
-
-def check_pos(model: str, v) -> str:
-    """The position encoding a job of ``model`` runs with ("sinusoid" when
-    ``v`` is None); ValueError for a value that is not one, or for a model
-    whose builder has no self-attention to rotate in."""
-    if v is None:
-        return "sinusoid"
-    if not isinstance(v, str) or v not in ("sinusoid", "rope"):
-        raise ValueError(f"pos must be 'sinusoid' or 'rope', got {v!r}")
-    if v not in getattr(MODELS[model].builder, "positions", ()):
-        raise ValueError(f"pos={v!r}: {model!r} has no position encoding to choose (the knob is for the "
-                         "Transformer models)")
-    return v
-
-
-def _check_trust_ratio(v) -> float:
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or not v > 0 or v == float("inf"):
-        raise ValueError(f"trust_ratio must be a finite number > 0, got {v!r}")
-    return float(v)
 
 
 def _cpu_trust_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, eta):
