@@ -1591,6 +1591,53 @@ void adam_bf16s_op(const Tensor& w, const Tensor& g, const Tensor& m, const Tens
                        (unsigned)(uint64_t)seed, (long)base, cur_stream(w), guard_ptr(guard, w), (long)zero_from,
                        (long)wd_until, clip_ptr(clip, w));
 }
+// 8-bit block-scaled optimizer state (optim_q8.hip): one int8 (first moment /
+// momentum) or uint8 (second moment) code tensor per moment, of at least
+// numel rounded up to the 256-element quantisation block, and ONE float32
+// [moments, blocks] tensor of block scales. The views cover the whole arena
+static void check_q8(const Tensor& w, const Tensor& g, const Tensor& wb,
+                     std::initializer_list<std::pair<const Tensor*, at::ScalarType>> codes, const Tensor& scales,
+                     int64_t step, int64_t zero_from, int64_t wd_until, const char* op) {
+  check_f32(w, "w"); check_f32(g, "g"); check_bf16(wb, "wb"); check_f32(scales, "scales");
+  check_contig(w, "w"); check_contig(g, "g"); check_contig(wb, "wb"); check_contig(scales, "scales");
+  TORCH_CHECK(w.numel() % 4 == 0 && g.numel() == w.numel() && wb.numel() == w.numel(), op, ": sizes");
+  TORCH_CHECK(g.device() == w.device() && wb.device() == w.device() && scales.device() == w.device(), op,
+              ": w, g, wb and scales must be on one device");
+  TORCH_CHECK(((((uintptr_t)w.data_ptr()) | ((uintptr_t)g.data_ptr())) & 15) == 0 &&
+                  (((uintptr_t)wb.data_ptr()) & 7) == 0, op, ": w / g must be 16-B aligned, wb 8-B aligned");
+  const int64_t nb = (w.numel() + 255) / 256;
+  for (const auto& c : codes) {
+    const Tensor& t = *c.first;
+    check_dev(t, "codes"); check_contig(t, "codes");
+    TORCH_CHECK(t.scalar_type() == c.second && t.numel() >= nb * 256 && (((uintptr_t)t.data_ptr()) & 3) == 0 &&
+                    t.device() == w.device(), op, ": codes must be ", c.second, " tensors of at least ", nb * 256,
+                " elements (numel rounded up to 256) on w's device, 4-B aligned");
+  }
+  TORCH_CHECK(scales.dim() == 2 && scales.size(0) == (int64_t)codes.size() && scales.size(1) >= nb, op,
+              ": scales must be float32 [", codes.size(), ", >= ", nb, "]");
+  TORCH_CHECK(zero_from % 4 == 0 && (wd_until < 0 || wd_until % 4 == 0), op, ": region bounds % 4");
+  TORCH_CHECK(step >= 1 && step <= 0x7fffffffLL, op, ": step must be a 1-based optimizer step, got ", step);
+}
+void sgd_q8_op(const Tensor& w, const Tensor& g, const Tensor& mq, const Tensor& scales, const Tensor& wb, double lr,
+               double momentum, double wd, double gscale, bool nesterov, bool zero_grad, int64_t seed, int64_t step,
+               const optional<Tensor>& guard, int64_t zero_from, int64_t wd_until, const optional<Tensor>& clip) {
+  check_q8(w, g, wb, {{&mq, at::kChar}}, scales, step, zero_from, wd_until, "tam.sgd_step_q8");
+  tam::sgd_step_q8(w.data_ptr<float>(), g.data_ptr<float>(), mq.data_ptr<int8_t>(), scales.data_ptr<float>(),
+                   bpm(wb), w.numel(), (float)lr, (float)momentum, (float)wd, (float)gscale, nesterov, zero_grad,
+                   (unsigned)(uint64_t)seed, (unsigned)step, cur_stream(w), guard_ptr(guard, w), (long)zero_from,
+                   (long)wd_until, clip_ptr(clip, w));
+}
+void adam_q8_op(const Tensor& w, const Tensor& g, const Tensor& mq, const Tensor& vq, const Tensor& scales,
+                const Tensor& wb, double lr, double b1, double b2, double eps, double wd, int64_t step,
+                double gscale, bool zero_grad, int64_t seed, const optional<Tensor>& guard, int64_t zero_from,
+                int64_t wd_until, const optional<Tensor>& clip) {
+  check_q8(w, g, wb, {{&mq, at::kChar}, {&vq, at::kByte}}, scales, step, zero_from, wd_until, "tam.adam_step_q8");
+  float* sc = scales.data_ptr<float>();
+  tam::adam_step_q8(w.data_ptr<float>(), g.data_ptr<float>(), mq.data_ptr<int8_t>(), vq.data_ptr<uint8_t>(), sc,
+                    sc + scales.size(1), bpm(wb), w.numel(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
+                    (int)step, (float)gscale, zero_grad, (unsigned)(uint64_t)seed, cur_stream(w),
+                    guard_ptr(guard, w), (long)zero_from, (long)wd_until, clip_ptr(clip, w));
+}
 // global-norm gradient clip (optim.hip): g -> one fp64 partial per block ->
 // the clip record the optimizer steps take
 void grad_sumsq_op(const Tensor& g, const Tensor& partials) {
@@ -2021,6 +2068,8 @@ TORCH_LIBRARY(tam, m) {
   m.def("sgd_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &sgd_op);
   m.def("adam_step(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adam_op);
   m.def("sgd_step_bf16s(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mom, Tensor(d!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, int seed, int step, int base=0, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &sgd_bf16s_op);
+  m.def("sgd_step_q8(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mq, Tensor(d!) scales, Tensor(e!) wb, float lr, float momentum, float wd, float gscale, bool nesterov, bool zero_grad, int seed, int step, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &sgd_q8_op);
+  m.def("adam_step_q8(Tensor(a!) w, Tensor(b!) g, Tensor(c!) mq, Tensor(d!) vq, Tensor(e!) scales, Tensor(f!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, int seed, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adam_q8_op);
   m.def("adam_step_bf16s(Tensor(a!) w, Tensor(b!) g, Tensor(c!) m, Tensor(d!) v, Tensor(e!) wb, float lr, float b1, float b2, float eps, float wd, int step, float gscale, bool zero_grad, int seed, int base=0, Tensor? guard=None, int zero_from=0, int wd_until=-1, Tensor? clip=None) -> ()", &adam_bf16s_op);
   m.def("grad_sumsq(Tensor g, Tensor(a!) partials) -> ()", &grad_sumsq_op);
   m.def("grad_clip_finalize(Tensor partials, float max_norm, float gscale, Tensor(a!) clip) -> ()", &grad_clip_finalize_op);

@@ -212,6 +212,20 @@ void adam_step_bf16s(float* w, float* g, bf16_t* m, bf16_t* v, bf16_t* wb, long 
                      float eps, float wd, int step, float gscale, int zero_grad, unsigned seed, long base,
                      hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
                      const float* clip = nullptr);
+// 8-bit block-scaled optimizer state (optim_q8.hip): the same steps with every
+// moment kept as one code byte per element (mq int8, vq uint8, >= n bytes) and
+// one fp32 scale per quantisation block of 256 arena elements (sm / sv,
+// >= ceil(n / 256) floats), stored with value-domain stochastic rounding on
+// the draws of the bf16-state contract. One launch over the WHOLE arena (a
+// block is an arena block; there is no base). step: the 1-based optimizer step
+void sgd_step_q8(float* w, float* g, int8_t* mq, float* sm, bf16_t* wb, long n, float lr, float momentum, float wd,
+                 float gscale, int nesterov, int zero_grad, unsigned seed, unsigned step, hipStream_t s,
+                 const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+                 const float* clip = nullptr);
+void adam_step_q8(float* w, float* g, int8_t* mq, uint8_t* vq, float* sm, float* sv, bf16_t* wb, long n, float lr,
+                  float b1, float b2, float eps, float wd, int step, float gscale, int zero_grad, unsigned seed,
+                  hipStream_t s, const unsigned* guard = nullptr, long zero_from = 0, long wd_until = -1,
+                  const float* clip = nullptr);
 // global-norm gradient clip: grad_sumsq writes one fp64 partial per block and
 // zeroes partials[blocks..slots); grad_clip_finalize sums them and writes the
 // 16-B clip record {float scale, float norm, u32 non-finite steps, u32

@@ -56,7 +56,8 @@ class CkptCostModel:
             return 0.0
         opt = "adam" if job.spec.model in ("transformer", "gnmt") else "sgd"
         # (a job that keeps bf16 optimizer state, JobSpec.opt_dtype, moves 2 B per moment;
-        # a factored one only its row and column means)
+        # a factored one only its row and column means, a q8 one 1 B per moment and
+        # one fp32 scale per 256 elements)
         return float(prof.state_bytes(opt, getattr(job.spec, "opt_dtype", None)))
 
     def on_preempt(self, job, alloc) -> Tuple[float, float]:

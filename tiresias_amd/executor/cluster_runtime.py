@@ -150,7 +150,7 @@ class ReplayJob:
     grad_clip: Optional[float] = None    # global-norm gradient clip of the job (None = off)
     dropout: Optional[float] = None      # training dropout of the job (None = off)
     attn_dropout: Optional[float] = None     # attention-probability dropout of the job (None = off)
-    opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" / "factored" (None = fp32)
+    opt_dtype: Optional[str] = None      # optimizer-state format of the job: "fp32" / "bf16" / "factored" / "q8" (None = fp32)
     trust_ratio: Optional[float] = None  # layer-wise trust coefficient of the job: LARS / LAMB (None = off)
     norm: Optional[str] = None           # normalisation of a CNN job: "batch" / "group" (None = batch)
     cardinality: Optional[int] = None    # ResNeXt cardinality of a ResNet job (None = the plain model)
@@ -1040,8 +1040,9 @@ class Worker:
         (Trainer.hbm_bytes: state + batch): the measured growth when one was
         last created here with the same optimizer-state format, else 1.5x its
         optimizer-inclusive state (bf16 moments priced at 2 B each, factored
-        state at its row and column means)."""
-        nk = (model, opt_dtype) if opt_dtype in ("bf16", "factored") else model
+        state at its row and column means, q8 moments at one byte each plus
+        one fp32 scale per 256 elements)."""
+        nk = (model, opt_dtype) if opt_dtype in ("bf16", "factored", "q8") else model
         if nk in self._need:
             return self._need[nk]
         from ..profiler.skew import model_profile
@@ -1222,7 +1223,7 @@ class Worker:
                         if grown > 0:      # a newly built trainer (not a warm-pool reuse)
                             # what _resident_bytes will count for it (state + batch)
                             odt = a.get("opt_dtype")
-                            nk = (a["model"], odt) if odt in ("bf16", "factored") else a["model"]
+                            nk = (a["model"], odt) if odt in ("bf16", "factored", "q8") else a["model"]
                             self._need[nk] = max(self._need.get(nk, 0.0), float(grown))
             elif src == "resident":
                 t = self.trainers.get(a["job"])

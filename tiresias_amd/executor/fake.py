@@ -62,7 +62,7 @@ def _state_bytes(model: str, opt_dtype: Optional[str] = None) -> float:
     except KeyError:
         return 0.0
     opt = MODELS[model].opt if model in MODELS else "sgd"
-    return float(prof.state_bytes(opt, opt_dtype))    # (bf16-state jobs: 2 B per moment; factored: row / column means)
+    return float(prof.state_bytes(opt, opt_dtype))    # (bf16-state jobs: 2 B per moment; factored: row / column means; q8: 1 B per moment + block scales)
 
 
 class FakeCluster:

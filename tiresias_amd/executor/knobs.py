@@ -120,7 +120,7 @@ def _factored_needs_adam(model: str, v) -> None:
         raise ValueError(f"opt_dtype 'factored' (Adafactor) needs an adam model, {model!r} is not one")
 
 
-_OPT_DTYPES = ("fp32", "bf16", "factored")
+_OPT_DTYPES = ("fp32", "bf16", "factored", "q8")
 _NORMS = ("batch", "group")
 _POSITIONS = ("sinusoid", "rope")
 
@@ -139,24 +139,29 @@ KNOBS: Dict[str, Knob] = {k.name: k for k in (
                        "(0 <= p < 1, quantised to 1/256: 0.1 drops 26/256); models without attention "
                        "dropout ignore it")),
     # format of the optimizer state (README "bf16 optimizer state", "Factored
-    # optimizer state"): bf16 state buffers cannot serve a fp32-state job, nor
-    # the reverse
-    Knob("opt_dtype", partial(_one_of, "opt_dtype", _OPT_DTYPES, "'fp32' or 'bf16', or 'factored' for an adam model"),
+    # optimizer state", "8-bit optimizer state"): the state buffers of one
+    # format cannot serve a job of another
+    Knob("opt_dtype", partial(_one_of, "opt_dtype", _OPT_DTYPES,
+                              "'fp32' or 'bf16', 'q8' for 8-bit block-scaled state, or 'factored' for an adam model"),
          applies=_factored_needs_adam, default="fp32", fixes="buffers", token="{}", label="{}-state",
          sharded={"bf16": "the sharded gang's slice launches and state all-gather are fp32-state only",
-                  "factored": "a sharded member holds only slices of the rows its row and column means run over"},
+                  "factored": "a sharded member holds only slices of the rows its row and column means run over",
+                  "q8": "a sharded member holds slices that cut the 256-element quantisation blocks"},
          cli=dict(choices=_OPT_DTYPES,
                   help="format of the optimizer state: bf16 keeps the moments in bf16 with stochastic "
                        "rounding (4 B per parameter less for Adam, 2 B for SGD, resident and spilled); "
                        "factored runs Adafactor on an Adam model (row and column means of the second "
                        "moment, no first moment: the state shrinks to O(rows + cols) per weight matrix; "
-                       "not combined with --trust-ratio); default fp32")),
+                       "not combined with --trust-ratio); q8 keeps Adam's or SGD's own update and stores "
+                       "every moment as one code byte per element plus one fp32 scale per 256 elements, with "
+                       "stochastic rounding (about 6 B per parameter less for Adam, 3 B for SGD; not combined "
+                       "with --trust-ratio); default fp32")),
     # layer-wise trust coefficient: LARS (sgd models) / LAMB (adam models)
     Knob("trust_ratio", partial(_finite_positive, "trust_ratio"),
          sharded="a sharded member holds only slices of the segments its norms run over",
          cli=dict(type=float, metavar="ETA",
                   help="layer-wise adaptive learning rates with trust coefficient ETA > 0: LARS for an SGD "
-                       "model, LAMB for an Adam model; not combined with --opt-dtype bf16")),
+                       "model, LAMB for an Adam model; not combined with --opt-dtype bf16 or q8")),
     # normalisation of a CNN job (README "GroupNorm"): "group" builds the
     # model with GroupNorm in place of every BatchNorm: other layers, no
     # running statistics
@@ -228,9 +233,9 @@ def check_together(values: Dict[str, Any]) -> None:
     knob and the model, such as opt_dtype "factored" on a model that is not
     an adam one, is the row's ``applies``.)"""
     if values.get("trust_ratio") is not None:
-        if values.get("opt_dtype") == "bf16":
-            raise ValueError("trust_ratio with opt_dtype='bf16' is not supported: LAMB's second pass would "
-                             "take the weights from the rounded moments")
+        if values.get("opt_dtype") in ("bf16", "q8"):
+            raise ValueError(f"trust_ratio with opt_dtype={values['opt_dtype']!r} is not supported: LAMB's second "
+                             "pass would take the weights from the rounded moments")
         if values.get("opt_dtype") == "factored":
             raise ValueError("trust_ratio with opt_dtype='factored' is not supported: LAMB's ratio is "
                              "defined over Adam's update")

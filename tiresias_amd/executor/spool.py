@@ -18,7 +18,7 @@ Request schema (JSON)::
      "grad_clip": null,             # global-norm gradient clip, a number > 0
      "dropout": null,               # training dropout probability, 0 <= p < 1
      "attn_dropout": null,          # attention-probability dropout, 0 <= p < 1 (quantised to 1/256)
-     "opt_dtype": null,             # optimizer-state format, "fp32", "bf16" or "factored" (null = fp32)
+     "opt_dtype": null,             # optimizer-state format, "fp32", "bf16", "factored" or "q8" (null = fp32)
      "trust_ratio": null}           # layer-wise trust coefficient > 0: LARS (sgd models) / LAMB (adam models)
 
 The keys from ``grad_clip`` on are the per-job training knobs: the rows of

@@ -71,6 +71,14 @@ class Trainer:
             # ONE fp32 tensor: every parameter's R row means and C column
             # means, in arena order, each slice padded to 64
             self._af_alloc()
+        elif self.opt_dtype == "q8":
+            # one code byte per element and moment (int8 first moment /
+            # momentum, uint8 second moment; whole quantisation blocks) and
+            # ONE fp32 [moments, blocks] tensor of block scales (optim_q8.hip)
+            nb = -(-n // Fx.Q8_BLOCK)
+            cdt = [torch.int8] if self.opt == "sgd" else [torch.int8, torch.uint8]
+            self.opt_state = [torch.zeros(nb * Fx.Q8_BLOCK, dtype=dt, device=self.device) for dt in cdt]
+            self.opt_state.append(torch.zeros(len(cdt), nb, dtype=torch.float32, device=self.device))
         else:
             self.opt_state = [torch.zeros(n, dtype=sdt, device=self.device)
                               for _ in range(1 if self.opt == "sgd" else 2)]
@@ -451,6 +459,18 @@ class Trainer:
                     T.adam_step_bf16s(A.master, A.grad, self.opt_state[0], self.opt_state[1], A.shadow, self.lr,
                                       0.9, 0.98, 1e-9, self.spec.wd, self.step_count, gscale, True, seed, 0,
                                       guard, zf, A.n_decay, clip)
+            elif self.opt_dtype == "q8":
+                # 8-bit block-scaled moments: same draws, rounded in the value
+                # domain between the two neighbouring codes; nothing is stored
+                seed = int(self.seed) & 0xFFFFFFFF
+                if self.opt == "sgd":
+                    T.sgd_step_q8(A.master, A.grad, self.opt_state[0], self.opt_state[1], A.shadow, self.lr, 0.9,
+                                  self.spec.wd, gscale, False, True, seed, self.step_count, guard, zf, A.n_decay,
+                                  clip)
+                else:
+                    T.adam_step_q8(A.master, A.grad, self.opt_state[0], self.opt_state[1], self.opt_state[2],
+                                   A.shadow, self.lr, 0.9, 0.98, 1e-9, self.spec.wd, self.step_count, gscale, True,
+                                   seed, guard, zf, A.n_decay, clip)
             elif self.opt == "sgd":
                 T.sgd_step(A.master, A.grad, self.opt_state[0], A.shadow, self.lr, 0.9, self.spec.wd, gscale, False,
                            True, guard, zf, A.n_decay, clip)
@@ -488,6 +508,12 @@ class Trainer:
                 A.grad.zero_()
                 A.shadow.copy_(A.master.to(torch.bfloat16))
                 self._af_stepped = True
+                regions = []
+            if self.opt_dtype == "q8" and regions:
+                # the device path in plain torch, ONE call over the arena:
+                # quantisation blocks are arena blocks
+                _cpu_opt_q8(self.opt, A.master, A.grad, self.opt_state, A.shadow, self.lr, self.spec.wd, gscale,
+                            self.step_count, self.seed, wd_until=A.n_decay)
                 regions = []
             if self.trust_ratio is not None and regions:
                 # the device path in plain torch, one decayed parameter at a
@@ -951,6 +977,46 @@ def _cpu_adafactor(w, g, rv, cv, lr, wd, gscale, step):
     s = float(torch.tensor(1.0 / max(1.0, rms), dtype=torch.float32))
     w.sub_(lr * (s * u + wd * w))
     return (float(torch.tensor(rms, dtype=torch.float32)), s)
+
+
+def _cpu_opt_q8(opt, w, g, state, wb, lr, wd, gscale, step, seed, zero_from=0, wd_until=-1):
+    """The q8-state step (optim_q8.hip) in plain torch over a WHOLE arena:
+    ``state`` is [m codes, (v codes,) scales]. The old moments are decoded
+    (Fx.q8_decode), updated in fp32 -- the weights come from the unrounded
+    moments, as in the kernels -- and stored back through Fx.q8_encode on the
+    draws of Fx.opt_state_draws. Weight decay applies below ``wd_until``, the
+    gradient is reset from ``zero_from`` on."""
+    n = w.numel()
+    scales = state[-1]
+    npad = scales.shape[1] * Fx.Q8_BLOCK
+    um, uv = Fx.opt_state_draws(0, npad, seed, step)
+    gg = g * gscale
+    wdv = torch.zeros_like(w)
+    wdv[:n if wd_until < 0 else wd_until] = wd
+    pad = torch.zeros(npad, dtype=torch.float32)
+    m = Fx.q8_decode(state[0], scales[0])[:n]
+    # the kernels' constants: fp32 b, and 1 - b formed from the fp32 b
+    b1, b2 = torch.tensor(0.9), torch.tensor(0.98)
+    if opt == "sgd":
+        m = b1 * m + (gg + wdv * w)
+        w.sub_(lr * m)
+    else:
+        v = Fx.q8_decode(state[1], scales[1])[:n]
+        m = b1 * m + (1.0 - b1) * gg
+        v = b2 * v + (1.0 - b2) * gg * gg
+        mh = m / (1 - 0.9 ** step)
+        vh = v / (1 - 0.98 ** step)
+        w.sub_(lr * (mh / (vh.sqrt() + 1e-9) + wdv * w))
+        pad[:n] = v
+        codes, s = Fx.q8_encode(pad, uv, True)
+        state[1].copy_(codes)
+        scales[1].copy_(s)
+    pad[:n] = m
+    codes, s = Fx.q8_encode(pad, um, False)
+    state[0].copy_(codes)
+    scales[0].copy_(s)
+    g[zero_from:].zero_()
+    wb.copy_(w.to(torch.bfloat16))
 
 
 def _cpu_opt(opt, w, g, state, lo, hi, wb, lr, wd, gscale, step, seed=None):

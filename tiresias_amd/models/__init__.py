@@ -54,7 +54,8 @@ class ModelSpec:
     attn_dropout: Optional[float] = None
     # format of the optimizer state (Trainer opt_dtype, --opt-dtype): None /
     # "fp32" keep fp32 moments, "bf16" keeps them in bf16 with stochastic
-    # rounding, "factored" runs Adafactor (adam models). No shipped model sets it
+    # rounding, "factored" runs Adafactor (adam models), "q8" keeps them as
+    # 8-bit block-scaled codes. No shipped model sets it
     opt_dtype: Optional[str] = None
     # layer-wise trust coefficient of the job's recipe (Trainer.set_trust_ratio,
     # --trust-ratio): LARS for an sgd model, LAMB for an adam model; None =

@@ -1169,6 +1169,72 @@ def sr_bf16(x: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     return ((r ^ 0x8000) - 0x8000).to(torch.int16).view(torch.bfloat16)
 
 
+# 8-bit block-scaled optimizer state (Trainer opt_dtype="q8";
+# csrc/kernels/optim_q8.hip): per quantisation block of Q8_BLOCK consecutive
+# arena elements and per moment, one fp32 scale (the block's max |value|) and
+# one code byte per element. First moment / SGD momentum: int8 q in [-127, 127]
+# decoding to sign(q) TM[|q|] scale with TM[k] = (k / 127)^2; Adam's second
+# moment: uint8 q in [0, 255] decoding to TV[q] scale with TV[k] = (k / 255)^4.
+# Encoding rounds stochastically between the two table neighbours of
+# |x| / scale, in the value domain, on the draws of opt_state_draws.
+Q8_BLOCK = 256
+_Q8_TABLES = None
+
+
+def q8_tables():
+    """(TM fp32 [128], TV fp32 [256]) on the CPU: formed in fp64 (d = k / N,
+    d2 = d * d, TM = d2, TV = d2 * d2) and rounded to fp32 once, the sequence
+    the kernels fill their LDS copies with."""
+    global _Q8_TABLES
+    if _Q8_TABLES is None:
+        dm = torch.arange(128, dtype=torch.float64) / 127.0
+        dv = torch.arange(256, dtype=torch.float64) / 255.0
+        dv2 = dv * dv
+        _Q8_TABLES = ((dm * dm).float(), (dv2 * dv2).float())
+    return _Q8_TABLES
+
+
+def q8_decode(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """fp32 values of ``codes`` (int8: first moment / momentum, uint8: second
+    moment; whole blocks) under the block ``scales``: one fp32 multiply
+    ``table[|code|] * scale``, then the sign."""
+    tm, tv = q8_tables()
+    c = codes.cpu().to(torch.int64).view(-1, Q8_BLOCK)
+    t = tv if codes.dtype == torch.uint8 else tm
+    val = t[c.abs()] * scales.cpu()[:c.shape[0], None]
+    return torch.where(c < 0, -val, val).reshape(-1)
+
+
+def q8_encode(x: torch.Tensor, u: torch.Tensor, second: bool):
+    """(codes, scales) of fp32 ``x`` (whole blocks on the CPU, missing
+    elements 0) with the 16-bit draws ``u`` (int64, x's shape): int8 codes of
+    a first moment / momentum, uint8 codes of a second moment (``second``).
+    The mirror of the kernels' encoder: scale = the block's max |x| (NaN
+    wins); a zero or non-finite scale gives codes 0; else y = min(|x| * (1 /
+    scale), 1), exactly 1 at the max, k with T[k] <= y <= T[k + 1], and the
+    code is k + 1 iff u * (T[k + 1] - T[k]) < (y - T[k]) * 65536. A nonzero
+    second moment never gets code 0."""
+    t = q8_tables()[1 if second else 0]
+    top = t.numel() - 1
+    xb = x.float().view(-1, Q8_BLOCK)
+    ax = xb.abs()
+    s = ax.amax(1)                                       # (amax propagates NaN)
+    live = (torch.isfinite(s) & (s > 0))[:, None]
+    sl = torch.where(live[:, 0], s, torch.ones_like(s))[:, None]
+    # (a subnormal scale is scaled up by 2^64 first, exactly: 1 / s would overflow)
+    pre = torch.where(sl < 2.0 ** -126, torch.full_like(sl, 2.0 ** 64), torch.ones_like(sl))
+    y = torch.where(ax == sl, torch.ones_like(ax), torch.minimum(ax * pre * (1.0 / (sl * pre)), torch.ones_like(ax)))
+    y = torch.where(live, y, torch.zeros_like(y))
+    k = (torch.searchsorted(t, y.contiguous(), right=True) - 1).clamp_(0, top - 1)
+    lo, hi = t[k], t[k + 1]
+    up = u.view_as(xb).float() * (hi - lo) < (y - lo) * 65536.0
+    c = torch.where(live, k + up.to(torch.int64), torch.zeros_like(k))
+    if second:
+        c = torch.where((c == 0) & (xb != 0) & live, torch.ones_like(c), c)
+        return c.to(torch.uint8).reshape(-1), s
+    return torch.where(xb < 0, -c, c).to(torch.int8).reshape(-1), s
+
+
 _DROP_REC: Optional[torch.Tensor] = None
 _DROP_SITE = 0
 _ATTN_DROP_SITE = 0

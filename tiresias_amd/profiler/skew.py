@@ -51,8 +51,13 @@ class ModelProfile:
             # Adafactor (an adam model's opt_dtype="factored"): row and column
             # means only, no first moment
             return self.params * (4 + 2) + self.factored * 4
+        moments = 1 if opt == "sgd" else 2
+        if opt_dtype == "q8":
+            # 8-bit block-scaled moments (opt_dtype="q8"): one code byte per
+            # element and one fp32 scale per 256 elements, per moment
+            return self.params * (4 + 2 + moments) + 4 * moments * -(-self.params // 256)
         per = 2 if opt_dtype == "bf16" else 4
-        return self.params * (4 + 2 + (1 if opt == "sgd" else 2) * per)
+        return self.params * (4 + 2 + moments * per)
 
 
 class _ShapeArena:

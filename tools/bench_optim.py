@@ -12,6 +12,12 @@ step with fp32 state against the step with bf16 state and Philox stochastic
 rounding (``*_step_bf16s``), interleaved, with the bytes each form moves per
 element (Adam 34 -> 26, SGD 26 -> 22).
 
+``--q8-state`` also times, per arena, the step with fp32 state, with bf16
+state and with 8-bit block-scaled state (``*_step_q8``, optim_q8.hip),
+interleaved, with the bytes each moves per element (Adam 34 / 26 / 22, SGD
+26 / 22 / 20). Every timed launch of this mode gets a fresh random gradient
+and a nonzero state, so that the q8 encoder has work.
+
 ``--trust-ratio`` also times, per arena with the model's real segment layout,
 the plain step against the layer-wise trust-ratio step of the same build
 (``lars_step`` on the SGD arenas, ``lamb_step`` on the Adam arenas: segmented
@@ -54,6 +60,9 @@ def main():
     bf16_rows = "--bf16-state" in sys.argv
     if bf16_rows:
         sys.argv.remove("--bf16-state")
+    q8_rows = "--q8-state" in sys.argv
+    if q8_rows:
+        sys.argv.remove("--q8-state")
     trust_rows = "--trust-ratio" in sys.argv
     if trust_rows:
         sys.argv.remove("--trust-ratio")
@@ -143,6 +152,69 @@ def main():
                     print(json.dumps(r), flush=True)
                     out.append(r)
             del mb, vb
+        if q8_rows:
+            nb = -(-n // 256)
+            k = 1 if opt == "sgd" else 2
+            mq = torch.zeros(256 * nb, device=dev, dtype=torch.int8)
+            vq = torch.zeros(256 * nb, device=dev, dtype=torch.uint8) if opt == "adam" else None
+            sc = torch.zeros(k, nb, device=dev)
+            mb = torch.zeros(n, device=dev, dtype=torch.bfloat16)
+            vb = torch.zeros(n, device=dev, dtype=torch.bfloat16) if opt == "adam" else None
+            step_no = [0]
+
+            def f32():
+                if opt == "sgd":
+                    T.sgd_step(w, g, m, wb, 0.1, 0.9, 1e-4, 1.0, False, True)
+                else:
+                    T.adam_step(w, g, m, v, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, 3, 1.0, True)
+
+            def b16():
+                step_no[0] += 1
+                if opt == "sgd":
+                    T.sgd_step_bf16s(w, g, mb, wb, 0.1, 0.9, 1e-4, 1.0, False, True, 1, step_no[0], 0)
+                else:
+                    T.adam_step_bf16s(w, g, mb, vb, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, step_no[0], 1.0, True, 1, 0)
+
+            def q8():
+                step_no[0] += 1
+                if opt == "sgd":
+                    T.sgd_step_q8(w, g, mq, sc, wb, 0.1, 0.9, 1e-4, 1.0, False, True, 1, step_no[0])
+                else:
+                    T.adam_step_q8(w, g, mq, vq, sc, wb, 1e-3, 0.9, 0.98, 1e-9, 0.01, step_no[0], 1.0, True, 1)
+
+            # Every step zeroes the gradient, and on a zero gradient with zero state the q8 encoder has nothing to
+            # do (a block whose max is 0 stores codes 0 without looking anything up). So every timed launch gets
+            # a fresh random gradient, refilled outside its event pair, after a 512 MiB write that takes the
+            # refilled lines out of the caches again; the warm launch leaves a nonzero state behind.
+            flush = torch.empty(1 << 29, device=dev, dtype=torch.uint8)
+
+            def timeit_live(fn, iters=20):
+                g.normal_()
+                fn()
+                evs = []
+                for _ in range(iters):
+                    g.normal_()
+                    flush.zero_()
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    fn()
+                    b.record()
+                    evs.append((a, b))
+                torch.cuda.synchronize()
+                return sum(a.elapsed_time(b) for a, b in evs) / iters * 1e3     # us
+
+            # bytes per element (the block scales add 8 k / 256)
+            per = {"sgd": (26, 22, 20), "adam": (34, 26, 22)}[opt]
+            for _ in range(3):                                                # three interleaved rounds
+                for kind, fn, bpe in (("fp32_state", f32, per[0]), ("bf16_state", b16, per[1]),
+                                      ("q8_state", q8, per[2])):
+                    us = timeit_live(fn)
+                    r = dict(model=name, opt=opt, kind=kind, params=n, bytes_per_elem=bpe, us=round(us, 1),
+                             tb_per_s=round(bpe * n / us / 1e6, 2))
+                    print(json.dumps(r), flush=True)
+                    out.append(r)
+            assert bool(torch.count_nonzero(mq)) and bool(torch.count_nonzero(sc))   # the encoder had work
+            del mq, vq, sc, mb, vb, flush
         if trust_rows:
             from tiresias_amd.models import make_model
             from tiresias_amd.ops.arena import Arena, _padded, trust_tile_table

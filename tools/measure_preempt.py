@@ -33,7 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="transformer,gnmt")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--opt-dtype", choices=("fp32", "bf16"), default=None,
+    ap.add_argument("--opt-dtype", choices=("fp32", "bf16", "q8"), default=None,
                     help="optimizer-state format of the measured trainers (default: the model's, fp32)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
